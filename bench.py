@@ -50,7 +50,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-from redtail_amd import capi, model_files, parallel, synth  # noqa: E402
+from redtail_amd import capi, parallel, synth  # noqa: E402
 
 W, H = 1257, 369
 MFMA_F32_PEAK_TFLOPS = 157.3          # /opt/skills/guides/MI355X_MICROARCH.md, chip-level parameters
@@ -83,18 +83,30 @@ def net_bytes_2d():
 
 
 def load_weights(half2):
-    """The reference's trained weight file (weights/_ref/, staged by __graft_entry__.build()) as (dict, description).
-    A missing file is not an error for a throughput benchmark, but the JSON line says which weights were timed."""
-    try:
-        path = model_files.weight_file("resnet18_2D", half2)
-        return capi.read_weights(path, half2), "reference ResNet-18_2D/TensorRT/%s" % os.path.basename(path)
-    except FileNotFoundError as e:
-        print("bench.py: %s -- timing seeded synthetic weights instead" % e, file=sys.stderr)
-        return synth.synth_weights_resnet18_2d(seed=7), "seeded He-normal (synthetic; reference weight file not staged)"
+    """(dict, description) of the timed weights: seeded synthetic, so that the inputs of a run -- and with --dump-outputs its outputs --
+    depend on the arguments alone (the reference's trained files are exercised by tests/test_net_parity.py).  In half2 mode the engine
+    rounds them to fp16 as it would the reference's fp16 file."""
+    return synth.synth_weights_resnet18_2d(seed=7), "seeded He-normal (synthetic)"
 
 
 def dominant(name):
     return "resblock" in name
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: writes every array as DIR/<name>.npy in float32.  An array beyond its share of the 64 MB budget is replaced
+    by a seeded sample of its elements (flattened, ascending positions): the same positions for the same shape on every run."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy().astype(np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 # a fused residual block (conv_s3rb_kernel): two of the 3x3 convolutions, x read once (with its halo), y written once
@@ -275,7 +287,7 @@ def trunk_bytes_3d(cfg, h, w, max_disp, es):
     return float(sum(per.values())), per
 
 
-def bench_3d(lib, dev, model, half2, b, steps, warmup, nctx, blob, weights, desc, world=1, distributed=False, rank=0, check=False):
+def bench_3d(lib, dev, model, half2, b, steps, warmup, nctx, blob, weights, desc, world=1, distributed=False, rank=0, check=False, dump=None):
     """One step = one IExecutionContext::enqueue of `b` stereo pairs through the whole 3-D network, inputs resident in HBM.
     Returns the JSON object (rank 0) or None."""
     w_img, h_img, max_disp, cfg_name = MODELS_3D[model]
@@ -311,6 +323,8 @@ def bench_3d(lib, dev, model, half2, b, steps, warmup, nctx, blob, weights, desc
         step(i)
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    if dump and rank == 0:
+        dump_outputs(dump, {"disparity": disps[(steps - 1) % nctx]})      # what the last timed step returned
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -459,14 +473,9 @@ def measured_traffic_launches(key, names):
 
 
 def weights_3d(model, half2):
-    """(weights dict, packed image, description) of a 3-D model: the reference's file where it ships one, seeded synthetic otherwise"""
+    """(weights dict, packed image, description) of a 3-D model: seeded synthetic, for the reason given at load_weights"""
     cfg = getattr(synth, MODELS_3D[model][3])
-    try:
-        path = model_files.weight_file(model, half2)
-        weights, desc = capi.read_weights(path, half2), "reference %s/TensorRT/%s" % (model, os.path.basename(path))
-    except FileNotFoundError as e:
-        print("bench.py: %s -- timing seeded synthetic weights instead" % e, file=sys.stderr)
-        weights, desc = synth.synth_weights_3d(cfg), "seeded He-normal (synthetic: the reference ships no such weight file)"
+    weights, desc = synth.synth_weights_3d(cfg), "seeded He-normal (synthetic)"
     return weights, capi.pack_weights(weights, fp16=half2), desc
 
 
@@ -480,7 +489,7 @@ def main_3d(args, rank, world, local_rank, dev, distributed):
     lib = capi.NetLib()
     lib.kernels.check(lib.kernels.lib.rt_set_device(local_rank), "rt_set_device")
     out = bench_3d(lib, dev, args.model, args.half2, args.batch, args.steps, args.warmup, args.contexts, blob, weights, desc,
-                   world=world, distributed=distributed, rank=rank, check=args.check)
+                   world=world, distributed=distributed, rank=rank, check=args.check, dump=args.dump_outputs)
     if out is not None:
         print(json.dumps(out))
 
@@ -657,6 +666,9 @@ def main():
     ap.add_argument("--model", default="resnet18_2D", choices=["resnet18_2D"] + sorted(MODELS_3D),
                     help="resnet18_2D (the headline) or one of the 3-D models (BASELINE configs C4 / C5): separate JSON line, HBM-priced roofline")
     ap.add_argument("--check", action="store_true", help="3-D models: also run the CPU oracle at the timed size (minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's disparity, float32) as DIR/disparity.npy; "
+                         "the inputs depend on the arguments alone, so two builds can be compared output for output")
     ap.add_argument("--from-host", action="store_true", help="also measure the PCIe-inclusive rate (extra JSON object)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
@@ -666,6 +678,8 @@ def main():
                          "of an idle MI355X needs ~50 ms of load to reach its sustained value (measured: 20 timed steps give 1883 / "
                          "1948 / 2015 pairs/s after 5 / 20 / 100 warm-up steps).  0 = off; reported on the JSON line")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.contexts <= 0:
         args.contexts = 3       # (six until the end of round 6: see --contexts; half2 used four two-stream contexts until its tower blocks were fused)
 
@@ -814,6 +828,7 @@ def main():
     issued = time.perf_counter() - t0                           # the host is done issuing: everything after this is the GPU finishing
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    last_disp = disps[(args.steps - 1) % nctx].clone() if args.dump_outputs else None      # what the last timed step returned
     # per rank: its own rate, the host time it needed to issue a step (23 launches through Python + ctypes) against the
     # step time -- the headroom one rank's host thread has -- and the cores it may use
     rank_rows = [{"rank": rank, "pairs_per_s": args.steps * b / elapsed, "weights_crc32": "%08x" % blob_crc,
@@ -1185,6 +1200,8 @@ def main():
             secondary = secondary_lines(lib, dev)
         if secondary is not None:
             out["secondary"] = secondary
+        if last_disp is not None:
+            dump_outputs(args.dump_outputs, {"disparity": last_disp})
         print(json.dumps(out), flush=True)
     for n in nets:
         n.destroy()

@@ -18,7 +18,7 @@ _nets = {}
 
 
 def real_weights(model, fp16=False):
-    """the reference's trained weight file (weights/_ref/, staged by build()); FileNotFoundError -- never a synthetic
+    """the reference's trained weight file (oracle/_ref/models/, staged by build()); FileNotFoundError -- never a synthetic
     fall-back -- when it is not there"""
     return O.read_weights(model_files.weight_file(model, fp16), fp16=fp16)
 

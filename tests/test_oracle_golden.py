@@ -316,8 +316,8 @@ def test_preprocessing_reproduces_the_reference_sample_input():
 
 
 def test_preprocessing_reproduces_both_reference_sample_inputs_in_full():
-    """the same on the complete files, both images, where the reference's data is staged (weights/_ref/sample: wherever build() ran with
-    /root/reference present; the snapshot that travels to the GPU box carries it)"""
+    """the same on the complete files, both images, where the reference's data is staged (oracle/_ref/sample_app/data: wherever build() ran with
+    the reference tree present)"""
     from PIL import Image
     from redtail_amd import model_files
     if model_files.sample_bin("left") is None:
