@@ -114,7 +114,13 @@ int rt_softargmax(const void* vol, void* out, int batch, int D, int H, int W, in
 int rt_corr_softargmax(const void* left, const void* right, void* out, int batch, int C, int H, int W,
                        int max_disp, int is_min, int64_t out_batch_stride, int dtype, rtStream stream);
 /* (fp32 maps of a network's size -- W >= 64, 16 <= C <= 32, max_disp <= 64 -- are correlated on the matrix cores through the 3-term fp16
- * split of the convolutions, inputs |x| < 65504; smaller ones by the fp32 fmaf chain of the reference kernel.)
+ * split of the convolutions; smaller ones by the fp32 fmaf chain of the reference kernel.)  Domain of that default path: every feature
+ * value |x| < 65504 (the fp16 range of the high part; rt_check_range checks it).  Outside it the result is inf or NaN where the fp32
+ * chain is finite -- a caller whose maps may leave the range passes RT_CONV_EXACT_FP32 to rt_corr_softargmax_flags.
+ * The same with flags: RT_CONV_EXACT_FP32 keeps the fp32 fmaf chain for maps of every size. */
+int rt_corr_softargmax_flags(const void* left, const void* right, void* out, int batch, int C, int H, int W,
+                             int max_disp, int is_min, int64_t out_batch_stride, int dtype, unsigned flags, rtStream stream);
+/*
  * Same with row pitches (elements, 0 = dense) for the feature maps and for the output plane; see
  * rt_conv_plan_set_pitch.  This entry always computes the fp32 chain: it is what engines built with
  * IBuilder::setExactFp32Mode call. */

@@ -68,6 +68,7 @@ KERNEL_SYMBOLS = {
     "rt_cost_volume": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
     "rt_softargmax": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
     "rt_corr_softargmax": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_int64, c_int, c_void_p]),
+    "rt_corr_softargmax_flags": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_int64, c_int, ctypes.c_uint, c_void_p]),
     "rt_corr_softargmax_pitched": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 8 + [c_int64, c_int, c_void_p]),
     "rt_corr_softargmax_il": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 8 + [c_int64, c_void_p]),
     "rt_corr_softargmax_il_slot": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 8 + [c_int64, c_int, c_void_p]),
@@ -220,9 +221,11 @@ class KernelLib:
         self.check(self.lib.rt_softargmax(_ptr(vol), _ptr(out), batch, D, H, W, int(is_min), dtype, stream),
                    "rt_softargmax")
 
-    def corr_softargmax(self, l, r, out, batch, C, H, W, D, is_min, out_bstride=0, dtype=RT_F32, stream=None):
-        self.check(self.lib.rt_corr_softargmax(_ptr(l), _ptr(r), _ptr(out), batch, C, H, W, D, int(is_min),
-                                               out_bstride, dtype, stream), "rt_corr_softargmax")
+    def corr_softargmax(self, l, r, out, batch, C, H, W, D, is_min, out_bstride=0, dtype=RT_F32, stream=None, flags=0):
+        self.check(self.lib.rt_corr_softargmax_flags(_ptr(l), _ptr(r), _ptr(out), batch, C, H, W, D, int(is_min), out_bstride, dtype,
+                                                     flags, stream)
+                   if flags else self.lib.rt_corr_softargmax(_ptr(l), _ptr(r), _ptr(out), batch, C, H, W, D, int(is_min),
+                                                             out_bstride, dtype, stream), "rt_corr_softargmax")
 
     def permute4d(self, x, y, batch, dims, order, dtype=RT_F32, stream=None):
         o = (c_int * 4)(*order)

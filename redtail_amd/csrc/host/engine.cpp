@@ -941,6 +941,9 @@ void EngineImpl::assignPitch() {
             if (op.kind == OpKind::kCorrSoftargmax) {
                 if (il[root(op.in[0])] != il[root(op.in[1])]) { il[root(op.in[0])] = il[root(op.in[1])] = 0; changed = true; }
                 if (il[op.out] && !il[root(op.in[0])]) { il[op.out] = 0; changed = true; }     // no interleaved map without the matrix-core kernel
+                // exact-fp32 engines correlate planar maps: rt_corr_softargmax_pitched is the fp32 fmaf chain, the matrix-core kernels of
+                // interleaved maps the 3-term fp16 split with its |x| < 65504 domain (include/rt_stereo.h)
+                if (exact_fp32_ && (il[root(op.in[0])] || il[op.out])) { il[root(op.in[0])] = il[root(op.in[1])] = il[op.out] = 0; changed = true; }
             }
         for (size_t ci = 0; ci < ops_.size(); ci++) {    // a concatenation and all its members, or none of them
             if (!cat_il[ci]) continue;

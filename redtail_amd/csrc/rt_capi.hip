@@ -293,6 +293,10 @@ extern "C" int rt_activation(const void* x, void* y, int64_t n, int act, int dty
 // cost volumes / soft-argmax
 // =================================================================================================
 namespace {
+int env_int(const char* name, int dflt);     // (development knobs, defined with the convolution plans below)
+// RT_CONV_TRACE for the correlation entries, which have no plan to cache it in: one line per launch on stderr
+bool corr_trace() { return env_int("RT_CONV_TRACE", 0) != 0; }
+
 template <bool FUSED, bool ISMIN, bool H2 = false, typename T = float>
 int launch_corr(const float* l, const float* r, float* out, int batch, int C, int H, int W, int D, int64_t obs,
                 hipStream_t st, int in_pitch = 0, int out_pitch = 0) {
@@ -300,7 +304,11 @@ int launch_corr(const float* l, const float* r, float* out, int batch, int C, in
     const int dt = std::min(16, rt::round_up((int)rt::cdiv(D, 4), 4));
     if (FUSED && D > 4 * dt) return fail(RT_E_UNSUPPORTED, "fused corr+softargmax supports max_disp <= 64 (got %d)", D);
     dim3 grid((unsigned)rt::cdiv(W, rt::kCorrTX), (unsigned)rt::cdiv(H, rt::kCorrRY), (unsigned)batch);
+    const bool trace = corr_trace();
     for (int d_base = 0; d_base < D; d_base += 4 * dt) {
+        if (trace)
+            fprintf(stderr, "[rt] corr_f32<%d,%d,%d,%d,%s> grid %u x %u x %u d_base %d\n", dt, (int)FUSED, (int)ISMIN, (int)H2,
+                    sizeof(T) == 2 ? "f16" : "f32", grid.x, grid.y, grid.z, d_base);
         switch (dt) {
             case 4: hipLaunchKernelGGL((rt::corr_f32_kernel<4, FUSED, ISMIN, H2, T>), grid, dim3(256), 0, st, l, r, out, C, H, W, D, d_base, obs, ip, op); break;
             case 8: hipLaunchKernelGGL((rt::corr_f32_kernel<8, FUSED, ISMIN, H2, T>), grid, dim3(256), 0, st, l, r, out, C, H, W, D, d_base, obs, ip, op); break;
@@ -312,8 +320,6 @@ int launch_corr(const float* l, const float* r, float* out, int batch, int C, in
     return 0;
 }
 }  // namespace
-
-namespace { int env_int(const char* name, int dflt); }      // (development knobs, defined with the convolution plans below)
 
 extern "C" int rt_corr_cost_volume(const void* left, const void* right, void* cv, int batch, int C, int H, int W,
                                    int D, int dtype, int format, rtStream s) {
@@ -341,6 +347,7 @@ extern "C" int rt_corr_cost_volume_flags(const void* left, const void* right, vo
         const int64_t tasks = (int64_t)a.blocks_x * H * batch;
         RT_REQUIRE(rt::cdiv(tasks, 4) < (1ll << 31), "rt_corr_cost_volume: grid too large");
         const dim3 grid((unsigned)(rt::cdiv(rt::cdiv(tasks, 4), 8) * 8));        // a multiple of 8: the kernel renumbers workgroups per XCD
+        if (corr_trace()) fprintf(stderr, "[rt] corr_mfma_planar grid %u\n", grid.x);
         hipLaunchKernelGGL(rt::corr_mfma_planar_kernel, grid, dim3(256), 0, S(s), a);
         RT_LAUNCH_CHECK("corr_mfma_planar_kernel");
         return 0;
@@ -394,6 +401,7 @@ extern "C" int rt_corr_softargmax_il_slot(const void* left, const void* right, v
     const int64_t tasks = (int64_t)a.blocks_x * H * batch;
     RT_REQUIRE(rt::cdiv(tasks, 4) < (1ll << 31), "rt_corr_softargmax_il: grid too large");
     dim3 grid((unsigned)rt::cdiv(tasks, 4));
+    if (corr_trace()) fprintf(stderr, "[rt] corr_softargmax_mfma<%d,0> grid %u slot %d\n", is_min ? 1 : 0, grid.x, out_slot);
     if (is_min) hipLaunchKernelGGL((rt::corr_softargmax_mfma_kernel<true>), grid, dim3(256), 0, S(s), a);
     else hipLaunchKernelGGL((rt::corr_softargmax_mfma_kernel<false>), grid, dim3(256), 0, S(s), a);
     RT_LAUNCH_CHECK("corr_softargmax_mfma_kernel");
@@ -421,6 +429,7 @@ extern "C" int rt_corr_softargmax_il8_f16(const void* left, const void* right, v
     const int64_t tasks = (int64_t)a.blocks_x * H * batch;
     RT_REQUIRE(rt::cdiv(tasks, 4) < (1ll << 31), "rt_corr_softargmax_il8_f16: grid too large");
     dim3 grid((unsigned)rt::cdiv(tasks, 4));
+    if (corr_trace()) fprintf(stderr, "[rt] corr_softargmax_mfma_f16<%d> grid %u slot %d\n", is_min ? 1 : 0, grid.x, out_slot);
     if (is_min) hipLaunchKernelGGL((rt::corr_softargmax_mfma_f16_kernel<true>), grid, dim3(256), 0, S(s), a);
     else hipLaunchKernelGGL((rt::corr_softargmax_mfma_f16_kernel<false>), grid, dim3(256), 0, S(s), a);
     RT_LAUNCH_CHECK("corr_softargmax_mfma_f16_kernel");
@@ -429,6 +438,11 @@ extern "C" int rt_corr_softargmax_il8_f16(const void* left, const void* right, v
 
 extern "C" int rt_corr_softargmax(const void* left, const void* right, void* out, int batch, int C, int H, int W,
                                   int D, int is_min, int64_t out_bstride, int dtype, rtStream s) {
+    return rt_corr_softargmax_flags(left, right, out, batch, C, H, W, D, is_min, out_bstride, dtype, 0u, s);
+}
+
+extern "C" int rt_corr_softargmax_flags(const void* left, const void* right, void* out, int batch, int C, int H, int W,
+                                        int D, int is_min, int64_t out_bstride, int dtype, unsigned flags, rtStream s) {
     RT_REQUIRE(left && right && out, "rt_corr_softargmax: null pointer");
     RT_REQUIRE(batch > 0 && C > 0 && H > 0 && W > 0 && D > 0, "rt_corr_softargmax: bad dims");
     if (dtype != RT_F32) return fail(RT_E_UNSUPPORTED, "rt_corr_softargmax: only fp32 in this build");
@@ -436,7 +450,7 @@ extern "C" int rt_corr_softargmax(const void* left, const void* right, void* out
     // maps of a network's size: the Gram band on the matrix cores from planar maps (corr_softargmax_mfma_kernel<.., PLANAR>, the 3-term
     // fp16 split of the engines' correlation: |x| < 65504).  Small maps, D > 64, C > 32 and RT_CONV_EXACT_FP32 keep the fp32 fmaf kernel --
     // as does rt_corr_softargmax_pitched, the entry exact-fp32 engines call.
-    if (C >= 16 && C <= 32 && W >= 64 && D <= 64 && (int64_t)C * H * W < (1ll << 29) && env_int("RT_CONV_EXACT_FP32", 0) == 0 &&
+    if (C >= 16 && C <= 32 && W >= 64 && D <= 64 && (int64_t)C * H * W < (1ll << 29) && !(flags & RT_CONV_EXACT_FP32) && env_int("RT_CONV_EXACT_FP32", 0) == 0 &&
         env_int("RT_NO_CORR_MFMA_PLANAR", 0) == 0) {
         rt::CorrMfmaArgs a;
         a.left = static_cast<const float*>(left); a.right = static_cast<const float*>(right); a.out = static_cast<float*>(out);
@@ -449,6 +463,7 @@ extern "C" int rt_corr_softargmax(const void* left, const void* right, void* out
         const int64_t tasks = (int64_t)a.blocks_x * H * batch;
         RT_REQUIRE(rt::cdiv(tasks, 4) < (1ll << 31), "rt_corr_softargmax: grid too large");
         dim3 grid((unsigned)rt::cdiv(tasks, 4));
+        if (corr_trace()) fprintf(stderr, "[rt] corr_softargmax_mfma<%d,1> grid %u slot 1\n", is_min ? 1 : 0, grid.x);
         if (is_min) hipLaunchKernelGGL((rt::corr_softargmax_mfma_kernel<true, true>), grid, dim3(256), 0, S(s), a);
         else hipLaunchKernelGGL((rt::corr_softargmax_mfma_kernel<false, true>), grid, dim3(256), 0, S(s), a);
         RT_LAUNCH_CHECK("corr_softargmax_mfma_kernel<planar>");
@@ -1066,11 +1081,15 @@ bool drop_structural_zeros(std::vector<float>& packed) {
 }
 
 // conv_s3_kernel with ks contraction groups per workgroup (clamped to what the instantiation's LDS and register budget allow)
+template <typename T> constexpr const char* type_tag() { return sizeof(T) == 2 ? "f16" : "f32"; }
 template <int KH, int KW, int S, bool XIL, bool YIL, int NW = 4, typename TIN = float, typename TOUT = float>
-void launch_s3(dim3 grid, int ks, int64_t per_cu, hipStream_t st, const rt::ConvArgs& a) {
+void launch_s3(dim3 grid, int ks, int64_t per_cu, hipStream_t st, const rt::ConvArgs& a, int trace = 0) {
     using Cfg = rt::S3Cfg<KH, KW, S, NW>;
     ks = Cfg::max_groups(ks);                                  // per_cu: a sample's workgroups per CU; co-resident ones share 160 KB
     while (ks > 1 && std::min<int64_t>(per_cu, 4) * ks * Cfg::GRP_BYTES > 160 * 1024) ks = Cfg::max_groups(ks - 1);
+    if (trace)      // RT_CONV_TRACE: the instantiation, the grid as launched and the split-K after clamping
+        fprintf(stderr, "[rt] conv_s3<%d,%d,%d,%d,%d,%d,%s,%s> r%d grid %u x %u x %u ks %d\n", KH, KW, S, (int)XIL, (int)YIL, NW, type_tag<TIN>(),
+                type_tag<TOUT>(), a.r_il8, grid.x, grid.y, grid.z, ks);
 #ifndef HIPEMU
     // dynamic LDS beyond the default limit: a function attribute is per device (the one-process multi-GPU app), set once each
     static std::atomic<unsigned long long> done{0};
@@ -1675,15 +1694,24 @@ int enqueue_fold_factor(const rtConvPlan* plan, const void* x, void* y, int batc
     if (int rc = rt_conv_enqueue_hint(ff->pl, x, const_cast<float*>(a.a), nullptr, batch, s, hints)) return rc;
     if (int rc = rt_conv_enqueue_hint(ff->pr, a.x + (int64_t)ff->F * ff->H * ff->W, const_cast<float*>(a.c), nullptr, batch, s, hints)) return rc;
     const dim3 tgrid((unsigned)rt::cdiv(ff->W + 2, 256), (unsigned)ff->H, (unsigned)(batch * (ff->K / G)));
-    if (G == 8) hipLaunchKernelGGL(rt::fold_t_kernel<8>, tgrid, dim3(256), 0, S(s), a);
-    else hipLaunchKernelGGL(rt::fold_t_kernel<4>, tgrid, dim3(256), 0, S(s), a);
-    RT_LAUNCH_CHECK("fold_t_kernel");
-    hipLaunchKernelGGL(rt::fold_edge_kernel, dim3((unsigned)rt::cdiv(ff->H * (ff->K / 4), 64), (unsigned)ff->D, (unsigned)batch), dim3(256), 0, S(s), a);
-    RT_LAUNCH_CHECK("fold_edge_kernel");
+    const dim3 egrid((unsigned)rt::cdiv(ff->H * (ff->K / 4), 64), (unsigned)ff->D, (unsigned)batch);
     // the combining pass over x < W - 1, then the last column (edge term) -- see fold_combine_kernel
     const dim3 grid((unsigned)rt::cdiv(ff->W - 1, 256), (unsigned)ff->H, (unsigned)(batch * (ff->K / G)));
     const dim3 lgrid((unsigned)rt::cdiv((int64_t)ff->H * ff->D * (ff->K / G) * batch, 256), 1u, 1u);
     const int U = plan->opt_fold_u;
+    if (plan->opt_trace) {
+        const char* T = sc.y_f16 ? "f16" : "f32";
+        const int U1 = U == 4 ? 4 : (U == 2 ? 2 : 1);
+        fprintf(stderr, "[rt] fold_t<%d> grid %u x %u x %u\n", G, tgrid.x, tgrid.y, tgrid.z);
+        fprintf(stderr, "[rt] fold_edge grid %u x %u x %u\n", egrid.x, egrid.y, egrid.z);
+        if (ff->W > 1) fprintf(stderr, "[rt] fold_combine<%s,%d,%d,0> grid %u x %u x %u\n", T, sc.y_il8, U1, grid.x, grid.y, grid.z);
+        fprintf(stderr, "[rt] fold_combine<%s,%d,1,1> grid %u x %u x %u\n", T, sc.y_il8, lgrid.x, lgrid.y, lgrid.z);
+    }
+    if (G == 8) hipLaunchKernelGGL(rt::fold_t_kernel<8>, tgrid, dim3(256), 0, S(s), a);
+    else hipLaunchKernelGGL(rt::fold_t_kernel<4>, tgrid, dim3(256), 0, S(s), a);
+    RT_LAUNCH_CHECK("fold_t_kernel");
+    hipLaunchKernelGGL(rt::fold_edge_kernel, egrid, dim3(256), 0, S(s), a);
+    RT_LAUNCH_CHECK("fold_edge_kernel");
 #define RT_FOLD_COMBINE(T, il, u)                                                                          \
     do {                                                                                                   \
         if (ff->W > 1) hipLaunchKernelGGL((rt::fold_combine_kernel<T, il, u, false>), grid, dim3(256), 0, S(s), a); \
@@ -2625,6 +2653,10 @@ extern "C" int rt_conv_enqueue_ws(const rtConvPlan* plan, const void* x, void* y
             const int64_t gz = (int64_t)batch * a.Mz;
             RT_REQUIRE(gz <= 65535 && (a.Hx + 1) / 2 <= 65535, "rt_conv_enqueue: grid limit exceeded");
             dim3 grid((unsigned)rt::cdiv((a.Wx + 1) / 2, 256), (unsigned)((a.Hx + 1) / 2), (unsigned)gz);
+            // deconv3d_s2_small_kernel<C, second template argument, TIN, TOUT> -- the branches below, in their order
+            if (plan->opt_trace && !(sc.small3d == 1 && sc.x_il8))
+                fprintf(stderr, "[rt] deconv3d_s2_small<%d,%d,%s,%s> grid %u x %u x %u\n", a.C == 1 ? 1 : 2, sc.small3d == 1 ? 1 : 0,
+                        sc.x_f16 ? "f16" : "f32", (sc.small3d == 2 && sc.x_f16 && sc.y_f16) ? "f16" : "f32", grid.x, grid.y, grid.z);
             if (sc.small3d == 2 && sc.x_f16) {          // half2 mode: fp16 activations in, fp32 (binding) or fp16 out
                 if (sc.y_f16) {
                     if (a.C == 1) hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<1, false, _Float16, _Float16>), grid, dim3(256), 0, S(s), a);
@@ -2643,6 +2675,7 @@ extern "C" int rt_conv_enqueue_ws(const rtConvPlan* plan, const void* x, void* y
                     RT_REQUIRE(a.K == 32 && a.C == 1 && !a.resid && rowpairs <= 65535, "rt_conv_enqueue: plan lost the form its fused soft-argmax needs");
                     a.y_bstride = (int64_t)a.Hx * a.Wx;
                     dim3 gw((unsigned)rt::cdiv(groups, 4), (unsigned)rowpairs, (unsigned)batch);
+                    if (plan->opt_trace) fprintf(stderr, "[rt] deconv3d_s2_ilw<%d> grid %u x %u x %u segments 1 x %d\n", plan->softarg == 2 ? 2 : 1, gw.x, gw.y, gw.z, a.Mz);
                     if (plan->softarg == 2) hipLaunchKernelGGL(rt::deconv3d_s2_ilw_kernel<2>, gw, dim3(256), 0, S(s), a, a.Mz, 1);
                     else hipLaunchKernelGGL(rt::deconv3d_s2_ilw_kernel<1>, gw, dim3(256), 0, S(s), a, a.Mz, 1);
                 } else if (a.K == 32 && plan->opt_small_walk != 0) {
@@ -2654,9 +2687,11 @@ extern "C" int rt_conv_enqueue_ws(const rtConvPlan* plan, const void* x, void* y
                     nseg = (int)rt::cdiv(a.Mz, seg_len);
                     RT_REQUIRE(rowpairs <= 65535, "rt_conv_enqueue: grid limit exceeded");
                     dim3 gw((unsigned)(rt::cdiv(groups, 4) * nseg), (unsigned)rowpairs, (unsigned)batch);
+                    if (plan->opt_trace) fprintf(stderr, "[rt] deconv3d_s2_ilw<0> grid %u x %u x %u segments %d x %d\n", gw.x, gw.y, gw.z, nseg, seg_len);
                     hipLaunchKernelGGL(rt::deconv3d_s2_ilw_kernel<0>, gw, dim3(256), 0, S(s), a, seg_len, nseg);
                 } else {
                     dim3 g2((unsigned)(rt::cdiv(groups, 4 * rt::kSmallIlIters) * a.Mz), (unsigned)rowpairs, (unsigned)batch);
+                    if (plan->opt_trace) fprintf(stderr, "[rt] deconv3d_s2_il grid %u x %u x %u\n", g2.x, g2.y, g2.z);
                     hipLaunchKernelGGL(rt::deconv3d_s2_il_kernel, g2, dim3(256), 0, S(s), a);
                 }
             } else if (sc.small3d == 1 && !sc.x_f16 && sc.x_il8) {    // fp32 engines: (K/4, D, H, W, 4) in, split form on the matrix cores
@@ -2665,6 +2700,7 @@ extern "C" int rt_conv_enqueue_ws(const rtConvPlan* plan, const void* x, void* y
                 const int groups = (int)rt::cdiv((a.Wx + 1) / 2, 16);
                 RT_REQUIRE(batch <= 65535, "rt_conv_enqueue: grid limit exceeded");
                 dim3 g2((unsigned)(rt::cdiv(groups, 4 * rt::kSmallIlIters) * a.Mz), (unsigned)rt::cdiv((a.Hx + 1) / 2, 2), (unsigned)batch);
+                if (plan->opt_trace) fprintf(stderr, "[rt] deconv3d_s2_il4 grid %u x %u x %u\n", g2.x, g2.y, g2.z);
                 hipLaunchKernelGGL(rt::deconv3d_s2_il4_kernel, g2, dim3(256), 0, S(s), a);
             } else if (sc.small3d == 1 && sc.x_f16) {   // 3-D last layer in half2 mode: fp16 (K,D,H,W) in, fp32 volume out
                 if (a.C == 1) hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<1, true, _Float16, float>), grid, dim3(256), 0, S(s), a);
@@ -2719,7 +2755,7 @@ extern "C" int rt_conv_enqueue_ws(const rtConvPlan* plan, const void* x, void* y
             RT_REQUIRE((int64_t)batch * sc.nz <= 65535, "rt_conv_enqueue: grid limit exceeded");
             RT_REQUIRE(sc.y_cstride * (int64_t)sc.Cout < (1ll << 29), "rt_conv_enqueue: output sample exceeds 2 GB (32-bit buffer offsets)");
             dim3 g((unsigned)tiles, (unsigned)nblk, (unsigned)(batch * sc.nz));
-            if (plan->opt_trace) fprintf(stderr, "[rt] deconv_s3p grid %u x %u x %u r%d\n", g.x, g.y, g.z, sc.r_il8);
+            if (plan->opt_trace) fprintf(stderr, "[rt] deconv_s3p<%d> r%d grid %u x %u x %u\n", sc.y_il8 ? 1 : 0, sc.r_il8, g.x, g.y, g.z);
             if (sc.y_il8) hipLaunchKernelGGL(rt::deconv_s3p_kernel<true>, g, dim3(256), 0, S(s), a);
             else hipLaunchKernelGGL(rt::deconv_s3p_kernel<false>, g, dim3(256), 0, S(s), a);
             RT_LAUNCH_CHECK("deconv_s3p_kernel");
@@ -2732,7 +2768,6 @@ extern "C" int rt_conv_enqueue_ws(const rtConvPlan* plan, const void* x, void* y
             a.z_inner = plan->opt_zinner != 0 ? 1 : 0;
             RT_REQUIRE(batch <= 65535 && (int64_t)batch * sc.nz <= 65535, "rt_conv_enqueue: grid limit exceeded");
             dim3 g = a.z_inner ? dim3((unsigned)(tiles * sc.nz), (unsigned)nblk, (unsigned)batch) : dim3((unsigned)tiles, (unsigned)nblk, (unsigned)(batch * sc.nz));
-            if (plan->opt_trace) fprintf(stderr, "[rt] deconv_f16p grid %u x %u x %u\n", g.x, g.y, g.z);
             if (plan->opt_f16p_walk != 0 && (!plan->has_resid || sc.r_il8)) {       // (a planar skip tensor -- not what the executor uses -- stays with the per-depth kernel)
                 // the walk (deconv_f16pw_kernel): a workgroup keeps its tile and takes a segment of the class's output depths.  Segments as
                 // long as the grid allows: cost = rounds over the chip's 3 workgroups per CU x (slices per segment + one slice's worth of
@@ -2770,6 +2805,7 @@ extern "C" int rt_conv_enqueue_ws(const rtConvPlan* plan, const void* x, void* y
                 RT_LAUNCH_CHECK("deconv_f16pw_kernel");
                 continue;
             }
+            if (plan->opt_trace) fprintf(stderr, "[rt] deconv_f16p grid %u x %u x %u\n", g.x, g.y, g.z);
             hipLaunchKernelGGL(rt::deconv_f16p_kernel, g, dim3(256), 0, S(s), a);
             RT_LAUNCH_CHECK("deconv_f16p_kernel");
             continue;
@@ -2852,7 +2888,11 @@ extern "C" int rt_conv_enqueue_ws(const rtConvPlan* plan, const void* x, void* y
                 seg = seg < 4 ? 4 : (seg > 240 ? 240 : (seg + 3) / 4 * 4);
                 ra.seg = seg;
                 dim3 sgrid((unsigned)(ra.c.tiles_x * (int)rt::cdiv(sc.Ho, seg)), 1u, (unsigned)batch);
-                if (plan->opt_trace) fprintf(stderr, "[rt] conv_s3rb%c grid %u x %u split %d -> %d\n", plan->x_split ? 'd' : 's', sgrid.x, sgrid.z, plan->x_split, plan->y_split);
+                if (plan->opt_trace) {
+                    if (sc.x_f16) fprintf(stderr, "[rt] conv_f16rbd grid %u x %u x %u seg %d\n", sgrid.x, sgrid.y, sgrid.z, seg);
+                    else fprintf(stderr, "[rt] conv_s3rb%c<%d> grid %u x %u x %u seg %d\n", plan->x_split ? 'd' : 's', plan->y_split ? 1 : 0, sgrid.x,
+                                 sgrid.y, sgrid.z, seg);
+                }
                 if (sc.x_f16) {                         // half2 mode: fp16 tensors, fp16 operands
                     ra.w1 = plan->rbh_w1_dev; ra.c.w = plan->rbh_w2_dev;
                     hipLaunchKernelGGL(rt::conv_f16rbd_kernel, sgrid, dim3(512), 0, S(s), ra);
@@ -2888,14 +2928,13 @@ extern "C" int rt_conv_enqueue_ws(const rtConvPlan* plan, const void* x, void* y
 #endif
         }
         if (sc.s3first) {
+            if (plan->opt_trace) fprintf(stderr, "[rt] conv_s3_first<%d> grid %u x %u x %u twin %d\n", sc.y_il8 ? 1 : 0, grid.x, grid.y, grid.z, a.x2 ? 1 : 0);
             if (sc.y_il8) hipLaunchKernelGGL((rt::conv_s3_first_kernel<true>), grid, dim3(256), 0, S(s), a);
             else hipLaunchKernelGGL((rt::conv_s3_first_kernel<false>), grid, dim3(256), 0, S(s), a);
             RT_LAUNCH_CHECK("conv_s3_first_kernel");
             continue;
         }
         if (sc.split3) {
-            if (plan->opt_trace)
-                fprintf(stderr, "[rt] conv_s3 %dx%d s%d x%d y%d r%d grid %u x %u x %u\n", sc.KH, sc.KW, sc.S, sc.x_il8, sc.y_il8, sc.r_il8, grid.x, grid.y, grid.z);
             bool launched = false;
             // split-K for launches that leave SIMDs with a single wave (the low-resolution layers; conv_split.hip.h): KS groups of
             // 4 waves per workgroup, as many as the CU's 16 wave slots at this kernel's register budget allow.  Chosen from the
@@ -2907,22 +2946,21 @@ extern "C" int rt_conv_enqueue_ws(const rtConvPlan* plan, const void* x, void* y
             if (plan->opt_ksplit > 0 || (plan->opt_ksplit < 0 && !(hints & RT_HINT_THROUGHPUT))) {
                 const int nch = a.CinPad / 16;
                 ks = plan->opt_ksplit > 0 ? plan->opt_ksplit : (per_cu == 1 && nch >= 4 ? 4 : (per_cu <= 2 && nch >= 2 ? 2 : 1));
-                if (plan->opt_trace) fprintf(stderr, "[rt] conv_s3 split-K request %d\n", ks);
             }
             if (sc.x_f16 || sc.y_f16) {                 // fp16 storage (3-D tensors of half2 mode): planar, 4-row tiles
                 // (the residual's layout is a run-time flag of the kernel: r_il8; an interleaved fp16 OUTPUT exists for fp32 planar input)
                 if (!sc.x_f16 && sc.x_il8 && sc.KH == 3 && sc.KW == 3 && sc.S == 1 && sc.TY == 4 && sc.y_f16) {      // fp32 interleaved in (2-D tower tensor)
-                    if (sc.y_il8) launch_s3<3, 3, 1, true, true, 4, float, _Float16>(zfold(grid), ks, per_cu, S(s), a);
-                    else launch_s3<3, 3, 1, true, false, 4, float, _Float16>(zfold(grid), ks, per_cu, S(s), a);
+                    if (sc.y_il8) launch_s3<3, 3, 1, true, true, 4, float, _Float16>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);
+                    else launch_s3<3, 3, 1, true, false, 4, float, _Float16>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);
                     RT_LAUNCH_CHECK("conv_s3_kernel<float, f16>");
                     continue;
                 }
                 RT_REQUIRE(!sc.x_il8 && !(sc.y_il8 && sc.x_f16) && sc.TY == 4 && sc.y_f16, "rt_conv_enqueue: fp16-storage variant of the split kernel not instantiated");
 #define RT_S3H(kh, kw, st)                                                                                                         \
     if (!launched && sc.KH == kh && sc.KW == kw && sc.S == st) {                                                                   \
-        if (sc.x_f16) launch_s3<kh, kw, st, false, false, 4, _Float16, _Float16>(zfold(grid), ks, per_cu, S(s), a); \
-        else if (sc.y_il8) launch_s3<kh, kw, st, false, true, 4, float, _Float16>(zfold(grid), ks, per_cu, S(s), a); \
-        else launch_s3<kh, kw, st, false, false, 4, float, _Float16>(zfold(grid), ks, per_cu, S(s), a);   \
+        if (sc.x_f16) launch_s3<kh, kw, st, false, false, 4, _Float16, _Float16>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace); \
+        else if (sc.y_il8) launch_s3<kh, kw, st, false, true, 4, float, _Float16>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace); \
+        else launch_s3<kh, kw, st, false, false, 4, float, _Float16>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);   \
         launched = true;                                                                                                           \
     }
                 RT_S3H(3, 3, 1) RT_S3H(3, 3, 2) RT_S3H(1, 1, 1) RT_S3H(1, 2, 1) RT_S3H(2, 1, 1) RT_S3H(2, 2, 1)
@@ -2930,19 +2968,19 @@ extern "C" int rt_conv_enqueue_ws(const rtConvPlan* plan, const void* x, void* y
             }
 #ifdef RT_EXPERIMENTAL
             if (!launched && sc.KH == 3 && sc.KW == 3 && sc.S == 1 && sc.TY == 8) {          // 8-row tiles, 8 waves
-                if (sc.x_il8 && sc.y_il8) launch_s3<3, 3, 1, true, true, 8>(zfold(grid), ks, per_cu, S(s), a);
-                else if (sc.x_il8) launch_s3<3, 3, 1, true, false, 8>(zfold(grid), ks, per_cu, S(s), a);
-                else if (sc.y_il8) launch_s3<3, 3, 1, false, true, 8>(zfold(grid), ks, per_cu, S(s), a);
-                else launch_s3<3, 3, 1, false, false, 8>(zfold(grid), ks, per_cu, S(s), a);
+                if (sc.x_il8 && sc.y_il8) launch_s3<3, 3, 1, true, true, 8>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);
+                else if (sc.x_il8) launch_s3<3, 3, 1, true, false, 8>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);
+                else if (sc.y_il8) launch_s3<3, 3, 1, false, true, 8>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);
+                else launch_s3<3, 3, 1, false, false, 8>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);
                 launched = true;
             }
 #endif
 #define RT_S3(kh, kw, st)                                                                                                   \
     if (!launched && sc.KH == kh && sc.KW == kw && sc.S == st) {                                                            \
-        if (sc.x_il8 && sc.y_il8) launch_s3<kh, kw, st, true, true>(zfold(grid), ks, per_cu, S(s), a);        \
-        else if (sc.x_il8) launch_s3<kh, kw, st, true, false>(zfold(grid), ks, per_cu, S(s), a);              \
-        else if (sc.y_il8) launch_s3<kh, kw, st, false, true>(zfold(grid), ks, per_cu, S(s), a);              \
-        else launch_s3<kh, kw, st, false, false>(zfold(grid), ks, per_cu, S(s), a);                           \
+        if (sc.x_il8 && sc.y_il8) launch_s3<kh, kw, st, true, true>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);        \
+        else if (sc.x_il8) launch_s3<kh, kw, st, true, false>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);              \
+        else if (sc.y_il8) launch_s3<kh, kw, st, false, true>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);              \
+        else launch_s3<kh, kw, st, false, false>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);                           \
         launched = true;                                                                                                    \
     }
             RT_S3(3, 3, 1) RT_S3(3, 3, 2) RT_S3(1, 1, 1) RT_S3(1, 2, 1) RT_S3(2, 1, 1) RT_S3(2, 2, 1)
@@ -2952,16 +2990,13 @@ extern "C" int rt_conv_enqueue_ws(const rtConvPlan* plan, const void* x, void* y
             continue;
         }
         if (sc.f16first) {
-            if (plan->opt_trace) fprintf(stderr, "[rt] conv_f16_first il8 y%d grid %u x %u x %u\n", sc.y_il8, grid.x, grid.y, grid.z);
+            if (plan->opt_trace) fprintf(stderr, "[rt] conv_f16_first<%d> grid %u x %u x %u twin %d\n", sc.y_il8 ? 1 : 0, grid.x, grid.y, grid.z, a.x2 ? 1 : 0);
             if (sc.y_il8) hipLaunchKernelGGL((rt::conv_f16_first_kernel<true>), grid, dim3(256), 0, S(s), a, plan->cin);
             else hipLaunchKernelGGL((rt::conv_f16_first_kernel<false>), grid, dim3(256), 0, S(s), a, plan->cin);
             RT_LAUNCH_CHECK("conv_f16_first_kernel");
             continue;
         }
         if (sc.f16mma) {
-            if (plan->opt_trace)
-                fprintf(stderr, "[rt] conv_f16mma %dx%d s%d rows %d il8 x%d y%d r%d grid %u x %u x %u\n", sc.KH, sc.KW, sc.S, sc.TY, sc.x_il8,
-                        sc.y_il8, sc.r_il8, grid.x, grid.y, grid.z);
             // Conv3D 3x3x3 stride 1 between interleaved fp16 tensors: the workgroup walks down the depth axis (conv_f16dw.hip.h)
             if (plan->c3d_dw && plan->opt_dw != 0 && sc.KH == 3 && sc.KW == 3 && sc.S == 1 && sc.x_il8 && sc.y_il8 && !sc.zs_dev && sc.y_xstride == 1 &&
                 (!plan->has_resid || sc.r_il8) && (plan->act == RT_ACT_NONE || plan->act == RT_ACT_ELU) && !sc.shift_dev) {
@@ -2995,8 +3030,10 @@ extern "C" int rt_conv_enqueue_ws(const rtConvPlan* plan, const void* x, void* y
                 const int64_t gx = npairs * a.dw_nseg * a.nb_inner;
                 RT_REQUIRE(gx < (1ll << 31) && batch <= 65535, "rt_conv_enqueue: grid limit exceeded");
                 dim3 gd((unsigned)gx, 1u, (unsigned)batch);
-                if (plan->opt_trace) fprintf(stderr, "[rt] conv_f16dw grid %u x %u segments %d x %d slices, %d chunks per slice\n", gd.x, gd.z, a.dw_nseg, a.dw_seg, a.dw_cpc);
                 const bool resident = a.dw_cpc <= 2, elu = plan->act == RT_ACT_ELU;
+                if (plan->opt_trace)        // conv_f16dw_kernel<resident, has_resid, elu>
+                    fprintf(stderr, "[rt] conv_f16dw<%d,%d,%d> grid %u x %u segments %d x %d slices, %d chunks per slice\n", resident ? 1 : 0,
+                            plan->has_resid ? 1 : 0, elu ? 1 : 0, gd.x, gd.z, a.dw_nseg, a.dw_seg, a.dw_cpc);
 #define RT_DW_LAUNCH(res, hr, el) hipLaunchKernelGGL((rt::conv_f16dw_kernel<res, hr, el>), gd, dim3(512), 0, S(s), a)
                 if (resident) {
                     if (plan->has_resid) { if (elu) RT_DW_LAUNCH(true, true, true); else RT_DW_LAUNCH(true, true, false); }
@@ -3020,6 +3057,9 @@ extern "C" int rt_conv_enqueue_ws(const rtConvPlan* plan, const void* x, void* y
                 RT_LAUNCH_CHECK("conv_f16r4_kernel");
                 continue;
             }
+            if (plan->opt_trace)        // (after the two walks above: this line names the conv_f16mma_kernel launches below)
+                fprintf(stderr, "[rt] conv_f16mma %dx%d s%d rows %d il8 x%d y%d r%d grid %u x %u x %u\n", sc.KH, sc.KW, sc.S, sc.TY, sc.x_il8,
+                        sc.y_il8, sc.r_il8, grid.x, grid.y, grid.z);
             if (sc.KH == 3 && sc.KW == 3 && sc.S == 1) {     // the tower layers: tensor layouts x rows per workgroup
 #define RT_F16_331(xi, yi, nw)                                                                                   \
     if (sc.x_il8 == xi && sc.y_il8 == yi && sc.TY == nw) {                                                       \

@@ -7,13 +7,7 @@ import torch
 from oracle import stereo_oracle as O
 from redtail_amd import capi
 from test_ops_parity import T, near, rnd
-
-
-def pitched(a, pitch, fill=np.nan):
-    """(..., H, W) -> (..., H, pitch) with `fill` in the padding columns"""
-    out = np.full(a.shape[:-1] + (pitch,), fill, np.float32)
-    out[..., :a.shape[-1]] = a
-    return out
+from layouts import pitched
 
 
 CASES = [

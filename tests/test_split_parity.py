@@ -12,6 +12,7 @@ from redtail_amd import capi
 from test_ops_parity import rnd
 from test_pitch_parity import pitched
 from test_wino_parity import from_il, to_il
+from layouts import to_split, from_split
 
 
 def ref64(x, wt, b, res, act):
@@ -297,25 +298,6 @@ def test_split_resblock(backend, c, cmid, h, w, batch, pitch, il):
 
 
 # ---- the tower block on PRE-SPLIT tensors (conv_rbd.hip.h) ---------------------------------------------------------------------
-def to_split(a):
-    """(N, C, H, P) fp32 -> the pre-split tensor (N, C/8, H, P, [8 hi | 8 lo]) as an fp32-typed array (N, C/8, H, P, 8):
-    hi = fp16(v), lo = fp16((v - hi) * 2^11) (include/rt_stereo.h: rt_resblock_plan_set_split)"""
-    n, c, h, p = a.shape
-    g = a.reshape(n, c // 8, 8, h, p).transpose(0, 1, 3, 4, 2).astype(np.float32)
-    with np.errstate(invalid="ignore", over="ignore"):
-        hi = g.astype(np.float16)
-        lo = ((g - hi.astype(np.float32)) * np.float32(2048)).astype(np.float16)
-    return np.ascontiguousarray(np.concatenate([hi, lo], axis=-1)).view(np.float32)
-
-
-def from_split(a):
-    """the values a pre-split tensor holds, hi + lo * 2^-11, as (N, C, H, P) fp32"""
-    h16 = np.ascontiguousarray(a).view(np.float16)
-    n, g, h, p, _ = h16.shape
-    v = h16[..., :8].astype(np.float32) + h16[..., 8:].astype(np.float32) * np.float32(1 / 2048)
-    return v.transpose(0, 1, 4, 2, 3).reshape(n, g * 8, h, p)
-
-
 RBD_CASES = [
     # h, w, batch, pitch
     (16, 30, 1, 32),       # exactly one strip and one segment

@@ -10,6 +10,7 @@ import torch
 from oracle import stereo_oracle as O
 from redtail_amd import capi
 from test_ops_parity import T, near, rnd
+from layouts import to_il, from_il
 
 @pytest.fixture(autouse=True)
 def _winograd_only(monkeypatch):
@@ -87,17 +88,6 @@ def test_wino_conv3d(backend, monkeypatch, out_dchw):
         plan.destroy()
     near(outs[0], ref, 2e-5)
     near(outs[1], ref, 2e-5)
-
-
-def to_il(a, g):
-    """(N, C, H, P) planar -> (N, C/g, H, P, g) channel-interleaved"""
-    n, c, h, p = a.shape
-    return np.ascontiguousarray(a.reshape(n, c // g, g, h, p).transpose(0, 1, 3, 4, 2))
-
-
-def from_il(a):
-    n, q, h, p, g = a.shape
-    return a.transpose(0, 1, 4, 2, 3).reshape(n, q * g, h, p)
 
 
 IL_CASES = [
