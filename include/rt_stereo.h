@@ -169,6 +169,19 @@ int rt_concat_channels(const void* x, void* y, int batch, int C, int Ctot, int c
  * (sample_app/main.cpp:83-98; stereo_dnn_ros_node.cpp:42-103), on the device. */
 int rt_preprocess_bgr8(const void* src_u8, int src_h, int src_w, void* dst_f32, int dst_h, int dst_w, int batch,
                        rtStream stream);
+/* Colour encodings of sensor_msgs/Image the ROS node accepts (stereo_dnn_ros_node.cpp:112-119), plus rgba8. */
+enum { RT_ENC_BGR8 = 0, RT_ENC_RGB8 = 1, RT_ENC_BGRA8 = 2, RT_ENC_RGBA8 = 3 };
+/* Both frames of a stereo pair as the camera delivers them -> float RGB CHW (N, 3, dst_h, dst_w) in [0,1] each: the per-frame
+ * path of the ROS node's computeOutputs / preprocessImage (stereo_dnn_ros_node.cpp:42-58, 60-77: cvtColor(BGR2RGB / BGRA2RGB),
+ * convertTo(CV_32F), cv::resize(INTER_AREA), / 255, HWC -> CHW) in one launch for the whole pair batch.  Frame n of a side
+ * starts at `base + n * src_h * src_step` bytes, row y at `src_step * y` (the sensor_msgs/Image `step`; >= src_w * 3 or * 4).
+ * Alpha is dropped.  Bit-identical to rt_preprocess_bgr8 on the dense BGR form of the same pixels; the same limits
+ * (down-scaling or same size, factors <= 6, else RT_E_UNSUPPORTED). */
+int rt_preprocess_frames_u8(const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step, int encoding,
+                            void* left_f32, void* right_f32, int dst_h, int dst_w, int batch, rtStream stream);
+/* out = disp * scale, fp32, in place allowed: the ROS node's `output *= w` (stereo_dnn_ros_node.cpp:81) and the sample app's
+ * `img_f *= w` (sample_app/main.cpp:325-327) on the device. */
+int rt_disparity_scale(const void* disp_f32, void* out_f32, int64_t n, float scale, rtStream stream);
 /* disparity map -> 16-bit KITTI encoding: saturate_cast<ushort>(round(disp * scale)), scale = 256 (x width for the
  * normalised output of ResNet-18 2D), sample_app/main.cpp:324-330. */
 int rt_disparity_to_u16(const void* disp_f32, void* out_u16, int64_t n, float scale, rtStream stream);

@@ -67,6 +67,22 @@ int rt_net_create_opt(rtStereoNet** net, const rtNetOptions* options);
  * that HIP stream (IExecutionContext::enqueue). */
 int rt_net_execute(rtStereoNet* net, const void* left, const void* right, void* disp, int batch, rtStream stream);
 
+/* What rt_net_execute_frames writes into `disp`:
+ *   RT_DISP_NET         fp32, what rt_net_execute writes (ResNet-18 2D: disparity / width; 3-D models: pixels)
+ *   RT_DISP_PIXELS_F32  fp32 disparity in pixels: the ROS node's 32FC1 output (stereo_dnn_ros_node.cpp:81, 89); the sample app's
+ *                       scale per model (sample_app/main.cpp:325-327): x width for ResNet-18 2D, x 1 for NVSmall / NVTiny / ResNet-18 3D
+ *   RT_DISP_KITTI_U16   uint16, the sample app's 16-bit PNG values (main.cpp:321-330): rt_disparity_to_u16(disp, 256 x that scale) */
+enum { RT_DISP_NET = 0, RT_DISP_PIXELS_F32 = 1, RT_DISP_KITTI_U16 = 2 };
+/* The ROS node's per-frame path (stereo_dnn_ros_node.cpp:60-103) in one call: left_u8 / right_u8 are device batches of camera frames
+ * (rt_stereo.h: rt_preprocess_frames_u8 -- src_h x src_w pixels, rows src_step bytes apart, RT_ENC_* encoding), pre-processed to the
+ * network's size into fp32 buffers the net owns, run as rt_net_execute does into a disparity the net owns, then written to `disp` as
+ * `disp_kind` says.  The engine's three bindings never change, so graph mode (rt_net_set_graph) replays one graph whatever frame and
+ * output pointers the caller rotates through.  stream == NULL: synchronous (pre-processing on the NULL stream, IExecutionContext::execute,
+ * the output step, then a synchronisation); otherwise everything is asynchronous on that stream.  As with rt_net_execute, calls on one
+ * net are ordered by the caller.  Errors (batch > max_batch, unknown kind or encoding, unsupported scale factors) write nothing. */
+int rt_net_execute_frames(rtStereoNet* net, const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step,
+                          int encoding, void* disp, int disp_kind, int batch, rtStream stream);
+
 /* Per-launch timing through nvinfer1::IProfiler (single stream, one event pair per launch):
  * writes "name<TAB>milliseconds\n" lines into buf.  Returns 0 or an error. */
 int rt_net_profile(rtStereoNet* net, const void* left, const void* right, void* disp, int batch, char* buf,

@@ -19,6 +19,8 @@ RT_NCHW, RT_NC2HW2 = 0, 1
 RT_ACT_NONE, RT_ACT_ELU, RT_ACT_SIGMOID = 0, 1, 2
 
 
+RT_ENC_BGR8, RT_ENC_RGB8, RT_ENC_BGRA8, RT_ENC_RGBA8 = 0, 1, 2, 3     # sensor_msgs/Image encodings (rt_preprocess_frames_u8)
+ENC_BYTES = {RT_ENC_BGR8: 3, RT_ENC_RGB8: 3, RT_ENC_BGRA8: 4, RT_ENC_RGBA8: 4}
 RT_HINT_THROUGHPUT = 1     # include/rt_stereo.h
 RT_CONV_EXACT_FP32 = 1     # rtConv2dDesc.flags / rtConv3dDesc.flags / rtNetOptions.flags
 
@@ -87,6 +89,9 @@ KERNEL_SYMBOLS = {
                                                 c_void_p]),
     "rt_preprocess_bgr8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "rt_disparity_to_u16": (c_int, [c_void_p, c_void_p, c_int64, ctypes.c_float, c_void_p]),
+    "rt_preprocess_frames_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                        c_void_p]),
+    "rt_disparity_scale": (c_int, [c_void_p, c_void_p, c_int64, ctypes.c_float, c_void_p]),
     "rt_conv_plan_input_limit": (c_int, [c_void_p, POINTER(c_float)]),
     "rt_has_experimental": (c_int, []),
     "rt_graph_begin_capture": (c_int, [c_void_p]),
@@ -196,6 +201,15 @@ class KernelLib:
 
     def disparity_to_u16(self, disp, out, n, scale, stream=None):
         self.check(self.lib.rt_disparity_to_u16(_ptr(disp), _ptr(out), n, scale, stream), "rt_disparity_to_u16")
+
+    def preprocess_frames_u8(self, left, right, src_h, src_w, src_step, encoding, left_dst, right_dst, dst_h, dst_w, batch=1,
+                             stream=None):
+        """both frames of a pair batch, rows src_step bytes apart, RT_ENC_* encoding -> two (N,3,dst_h,dst_w) fp32 RGB batches"""
+        self.check(self.lib.rt_preprocess_frames_u8(_ptr(left), _ptr(right), src_h, src_w, src_step, encoding, _ptr(left_dst),
+                                                    _ptr(right_dst), dst_h, dst_w, batch, stream), "rt_preprocess_frames_u8")
+
+    def disparity_scale(self, disp, out, n, scale, stream=None):
+        self.check(self.lib.rt_disparity_scale(_ptr(disp), _ptr(out), n, scale, stream), "rt_disparity_scale")
 
     def corr_softargmax_pitched(self, l, r, out, batch, C, H, W, D, is_min, in_pitch, out_pitch, out_bstride=0,
                                 dtype=RT_F32, stream=None):
@@ -358,6 +372,7 @@ class ConvPlan:
 # whole-network ABI (include/rt_stereo_net.h, libnvstereo_inference.so)
 # ---------------------------------------------------------------------------------------------------
 RT_MODEL_RESNET18_2D, RT_MODEL_NVSMALL, RT_MODEL_NVTINY, RT_MODEL_RESNET18 = 0, 1, 2, 3
+RT_DISP_NET, RT_DISP_PIXELS_F32, RT_DISP_KITTI_U16 = 0, 1, 2          # rt_net_execute_frames: what `disp` receives
 MODEL_IDS = {"resnet18_2D": RT_MODEL_RESNET18_2D, "nvsmall": RT_MODEL_NVSMALL, "nvtiny": RT_MODEL_NVTINY,
              "resnet18": RT_MODEL_RESNET18}
 
@@ -368,6 +383,7 @@ NET_SYMBOLS = {
     "rt_net_serialize": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(c_size_t)]),
     "rt_net_create_from_plan": (c_int, [POINTER(c_void_p), c_void_p, c_size_t]),
     "rt_net_execute": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "rt_net_execute_frames": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_void_p]),
     "rt_net_profile": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_char_p, c_size_t]),
     "rt_net_num_layers": (c_int, [c_void_p]),
     "rt_net_num_launches": (c_int, [c_void_p]),
@@ -516,6 +532,38 @@ class StereoNet:
     def execute(self, left, right, disp, batch=1, stream=None):
         self.netlib.check(self.netlib.lib.rt_net_execute(self.handle, _ptr(left), _ptr(right), _ptr(disp), batch, stream),
                           "rt_net_execute")
+
+    def execute_frames(self, left_u8, right_u8, encoding, disp, kind=RT_DISP_PIXELS_F32, batch=1, stream=None, src_step=None,
+                       src_w=None):
+        """rt_net_execute_frames: two batches of camera frames in, disparity out.  Frames are uint8 torch device tensors (numpy arrays under
+        the emulator) of shape (N, H, W, C) -- dense, or a view of padded rows (the row stride is the step) -- or (N, H, step) raw rows, for
+        which src_w gives the width in pixels.  kind: RT_DISP_NET / RT_DISP_PIXELS_F32 (fp32, (N,1,h,w)) or RT_DISP_KITTI_U16 (16-bit)."""
+        bpp = ENC_BYTES.get(encoding)
+        if bpp is None:                              # the C entry refuses it too; the shape logic below needs the pixel size
+            raise RtError("rt_net_execute_frames: unknown encoding %r" % (encoding,))
+        shapes = []
+        for f in (left_u8, right_u8):
+            shape = tuple(f.shape)
+            strides = tuple(f.stride()) if hasattr(f, "stride") and callable(f.stride) else tuple(f.strides)     # torch: elements, numpy: bytes (uint8: same)
+            if len(shape) == 4:
+                if shape[3] != bpp or strides[3] != 1 or strides[2] != bpp:
+                    raise ValueError("frames of shape (N,H,W,C) need C = %d bytes per pixel, dense within a row" % bpp)
+                h, w, step = shape[1], shape[2], strides[1]
+            elif len(shape) == 3:
+                if src_w is None or strides[2] != 1:
+                    raise ValueError("frames of shape (N,H,step) need src_w and rows of contiguous bytes")
+                h, w, step = shape[1], src_w, strides[1]
+            else:
+                raise ValueError("frames must be (N,H,W,C) or (N,H,step) uint8")
+            if shape[0] < batch or (batch > 1 and strides[0] != h * step):
+                raise ValueError("frame batch must hold %d frames of %d rows of %d bytes back to back" % (batch, h, step))
+            shapes.append((h, w, step))
+        if shapes[0] != shapes[1]:
+            raise ValueError("left and right frames differ in size or step: %r vs %r" % tuple(shapes))
+        h, w, step = shapes[0]
+        step = step if src_step is None else src_step
+        self.netlib.check(self.netlib.lib.rt_net_execute_frames(self.handle, _ptr(left_u8), _ptr(right_u8), h, w, step, encoding,
+                                                                _ptr(disp), kind, batch, stream), "rt_net_execute_frames")
 
     def set_debug(self, on=True):
         """IExecutionContext::setDebugSync: synchronise every launch and range-check the input of every fp16-pipe convolution"""

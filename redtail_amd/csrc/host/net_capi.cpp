@@ -58,9 +58,15 @@ struct rtStereoNet {
     ICudaEngine* engine = nullptr;
     IExecutionContext* context = nullptr;
     int layers = 0, width = 0, height = 0, max_batch = 1;
+    int model = RT_MODEL_RESNET18_2D;
+    void* frame_in[2] = {nullptr, nullptr};       // rt_net_execute_frames: fp32 inputs and disparity for max_batch, made on first use
+    void* frame_disp = nullptr;
     ~rtStereoNet() {
         if (context) context->destroy();
         if (engine) engine->destroy();
+        rt_free(frame_in[0]);
+        rt_free(frame_in[1]);
+        rt_free(frame_disp);
     }
 };
 
@@ -95,7 +101,7 @@ int build(rtStereoNet** out, int model, int width, int height, int max_batch, in
     if (dtype != RT_F32 && dtype != RT_F16) return fail("rt_net_create: weights_dtype must be RT_F32 or RT_F16");
     std::unique_ptr<rtStereoNet> n(new rtStereoNet());
     n->blob = std::move(blob);
-    n->width = width; n->height = height; n->max_batch = max_batch;
+    n->width = width; n->height = height; n->max_batch = max_batch; n->model = model;
     if (!parseWeights(*n, dtype)) return fail("rt_net_create: malformed weight file (expected name\\0, uint32 count, data ...)");
     n->plugins = IPluginContainer::create(n->log);
     IBuilder* builder = createInferBuilder(n->log);
@@ -265,6 +271,12 @@ extern "C" int rt_net_create_from_plan(rtStereoNet** out, const void* plan, size
         n->engine->getBindingIndex("disp") != 2)
         return fail("rt_net_create_from_plan: unexpected bindings");
     n->max_batch = n->engine->getMaxBatchSize();
+    // a plan knows its input size; only ResNet-18 2D has one (rt_net_serialize fails for the 3-D models' plugins)
+    const Dims in = n->engine->getBindingDimensions(0);
+    if (in.nbDims != 3 || in.d[0] != 3 || in.d[1] < 1 || in.d[2] < 1) return fail("rt_net_create_from_plan: unexpected input binding");
+    n->height = in.d[1];
+    n->width = in.d[2];
+    n->model = RT_MODEL_RESNET18_2D;
     n->context = n->engine->createExecutionContext();
     if (!n->context) return fail("rt_net_create_from_plan: context creation failed");
     *out = n.release();
@@ -276,6 +288,40 @@ extern "C" int rt_net_execute(rtStereoNet* net, const void* left, const void* ri
     void* bindings[3] = {const_cast<void*>(left), const_cast<void*>(right), disp};
     const bool ok = stream ? net->context->enqueue(batch, bindings, (cudaStream_t)stream, nullptr) : net->context->execute(batch, bindings);
     if (!ok) return fail("rt_net_execute: " + net->log.last_error);
+    return 0;
+}
+
+// The ROS node's computeOutputs (stereo_dnn_ros_node.cpp:60-103) after the H2D copy of the raw frames, and the sample app's result path
+// (sample_app/main.cpp:321-330), on the device.
+extern "C" int rt_net_execute_frames(rtStereoNet* net, const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step,
+                                     int encoding, void* disp, int disp_kind, int batch, rtStream stream) {
+    if (!net || !net->context || !left_u8 || !right_u8 || !disp) return fail("rt_net_execute_frames: null pointer");
+    if (batch < 1 || batch > net->max_batch)
+        return fail("rt_net_execute_frames: batch " + std::to_string(batch) + " outside 1.." + std::to_string(net->max_batch));
+    if (disp_kind != RT_DISP_NET && disp_kind != RT_DISP_PIXELS_F32 && disp_kind != RT_DISP_KITTI_U16)
+        return fail("rt_net_execute_frames: unknown disp_kind " + std::to_string(disp_kind));
+    if (encoding < RT_ENC_BGR8 || encoding > RT_ENC_RGBA8) return fail("rt_net_execute_frames: unknown encoding " + std::to_string(encoding));
+    const int64_t pixels = (int64_t)net->height * net->width;
+    for (void** p : {&net->frame_in[0], &net->frame_in[1], &net->frame_disp}) {
+        const size_t bytes = (size_t)net->max_batch * pixels * (p == &net->frame_disp ? 1 : 3) * sizeof(float);
+        if (!*p && rt_malloc(p, bytes) != 0) return fail(std::string("rt_net_execute_frames: ") + rt_last_error_string());
+    }
+    // (argument errors of the pre-processing -- short step, up-scaling, factors above 6 -- are found before anything is written)
+    if (rt_preprocess_frames_u8(left_u8, right_u8, src_h, src_w, src_step, encoding, net->frame_in[0], net->frame_in[1], net->height,
+                                net->width, batch, stream) != 0)
+        return fail(std::string("rt_net_execute_frames: ") + rt_last_error_string());
+    void* bindings[3] = {net->frame_in[0], net->frame_in[1], net->frame_disp};
+    const bool ok = stream ? net->context->enqueue(batch, bindings, (cudaStream_t)stream, nullptr) : net->context->execute(batch, bindings);
+    if (!ok) return fail("rt_net_execute_frames: " + net->log.last_error);
+    // ResNet-18 2D's sigmoid output is disparity / width; the 3-D models' soft-argmin is in pixels (sample_app/main.cpp:325-327)
+    const float scale = net->model == RT_MODEL_RESNET18_2D ? (float)net->width : 1.f;
+    const int64_t n = batch * pixels;
+    int rc = 0;
+    if (disp_kind == RT_DISP_NET) rc = rt_memcpy_d2d(disp, net->frame_disp, (size_t)n * sizeof(float), stream);
+    else if (disp_kind == RT_DISP_PIXELS_F32) rc = rt_disparity_scale(net->frame_disp, disp, n, scale, stream);
+    else rc = rt_disparity_to_u16(net->frame_disp, disp, n, 256.f * scale, stream);
+    if (rc == 0 && !stream) rc = rt_stream_sync(nullptr);
+    if (rc != 0) return fail(std::string("rt_net_execute_frames: ") + rt_last_error_string());
     return 0;
 }
 

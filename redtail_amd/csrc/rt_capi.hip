@@ -633,6 +633,47 @@ extern "C" int rt_preprocess_bgr8(const void* src, int src_h, int src_w, void* d
     return 0;
 }
 
+// (stereo_dnn_ros_node.cpp:42-77): both frames of a pair, any of the node's colour encodings, pitched rows -- one launch
+extern "C" int rt_preprocess_frames_u8(const void* left, const void* right, int src_h, int src_w, int64_t src_step, int encoding,
+                                       void* left_dst, void* right_dst, int dst_h, int dst_w, int batch, rtStream s) {
+    RT_REQUIRE(left && right && left_dst && right_dst, "rt_preprocess_frames_u8: null pointer");
+    RT_REQUIRE(encoding >= RT_ENC_BGR8 && encoding <= RT_ENC_RGBA8, "rt_preprocess_frames_u8: unknown encoding %d", encoding);
+    RT_REQUIRE(src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0 && batch > 0 && batch <= 32767,
+               "rt_preprocess_frames_u8: bad dims");
+    const int bpp = encoding == RT_ENC_BGRA8 || encoding == RT_ENC_RGBA8 ? 4 : 3;
+    RT_REQUIRE(src_step >= (int64_t)src_w * bpp, "rt_preprocess_frames_u8: row step %lld is shorter than %d pixels of %d bytes",
+               (long long)src_step, src_w, bpp);
+    if (dst_h > src_h || dst_w > src_w)
+        return fail(RT_E_UNSUPPORTED, "rt_preprocess_frames_u8: INTER_AREA up-scaling (%dx%d -> %dx%d) is not implemented", src_w, src_h, dst_w, dst_h);
+    if ((float)src_w / dst_w > 6.f || (float)src_h / dst_h > 6.f)
+        return fail(RT_E_UNSUPPORTED, "rt_preprocess_frames_u8: scale factors above 6 are not implemented");
+    const bool rgb = encoding == RT_ENC_RGB8 || encoding == RT_ENC_RGBA8;
+    const bool aligned = bpp == 4 && ((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right) | (uintptr_t)src_step) & 3) == 0;
+    const dim3 grid((unsigned)rt::cdiv(dst_w, rt::kFramesCols), (unsigned)rt::cdiv(dst_h, rt::kFramesRows), (unsigned)(2 * batch));
+    const dim3 block(rt::kFramesCols * rt::kFramesRows);
+    const unsigned char *l8 = static_cast<const unsigned char*>(left), *r8 = static_cast<const unsigned char*>(right);
+    float *lf = static_cast<float*>(left_dst), *rf = static_cast<float*>(right_dst);
+    if (bpp == 3)
+        hipLaunchKernelGGL((rt::preprocess_frames_kernel<3, false>), grid, block, 0, S(s), l8, r8, src_h, src_w, src_step, rgb, lf, rf,
+                           dst_h, dst_w, batch);
+    else if (aligned)
+        hipLaunchKernelGGL((rt::preprocess_frames_kernel<4, true>), grid, block, 0, S(s), l8, r8, src_h, src_w, src_step, rgb, lf, rf,
+                           dst_h, dst_w, batch);
+    else
+        hipLaunchKernelGGL((rt::preprocess_frames_kernel<4, false>), grid, block, 0, S(s), l8, r8, src_h, src_w, src_step, rgb, lf, rf,
+                           dst_h, dst_w, batch);
+    RT_LAUNCH_CHECK("preprocess_frames_kernel");
+    return 0;
+}
+
+extern "C" int rt_disparity_scale(const void* disp, void* out, int64_t n, float scale, rtStream s) {
+    RT_REQUIRE(disp && out && n > 0, "rt_disparity_scale: bad arguments");
+    hipLaunchKernelGGL(rt::disparity_scale_kernel, dim3((unsigned)rt::cdiv(n, 256)), dim3(256), 0, S(s),
+                       static_cast<const float*>(disp), static_cast<float*>(out), n, scale);
+    RT_LAUNCH_CHECK("disparity_scale_kernel");
+    return 0;
+}
+
 extern "C" int rt_disparity_to_u16(const void* disp, void* out, int64_t n, float scale, rtStream s) {
     RT_REQUIRE(disp && out && n > 0, "rt_disparity_to_u16: bad arguments");
     hipLaunchKernelGGL(rt::disparity_u16_kernel, dim3((unsigned)rt::cdiv(n, 256)), dim3(256), 0, S(s),
