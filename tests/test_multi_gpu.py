@@ -277,7 +277,7 @@ def test_bench_multi_rank_startup_with_a_world_of_one():
     env.pop("RT_DEV_KNOBS", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "3",
-           "--no-secondary", "--no-cpu-baseline"]
+           "--full", "--no-secondary", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([x for x in out.stdout.splitlines() if x.startswith("{")][-1])

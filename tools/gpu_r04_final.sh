@@ -4,10 +4,10 @@ cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out/r04final; mkdir -p $O
 timeout 2400 python -m pytest tests/ -x -q -m gpu > $O/pytest.log 2>&1; tail -n 4 $O/pytest.log
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -n 2 $O/smoke.log
-python bench.py > $O/bench_plain.json 2> $O/bench_plain.err; tail -n 2 $O/bench_plain.err
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_20_5.json 2> /dev/null
-python bench.py --model nvsmall --half2 --batch 8 --steps 24 --warmup 3 --check > $O/bench_nvsmall_half2_b8.json 2> /dev/null
-python bench.py --model resnet18 --batch 4 --steps 20 --warmup 2 --check > $O/bench_resnet18_3d_b4.json 2> /dev/null
+python bench.py --full > $O/bench_plain.json 2> $O/bench_plain.err; tail -n 2 $O/bench_plain.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_20_5.json 2> /dev/null
+python bench.py --full --model nvsmall --half2 --batch 8 --steps 24 --warmup 3 --check > $O/bench_nvsmall_half2_b8.json 2> /dev/null
+python bench.py --full --model resnet18 --batch 4 --steps 20 --warmup 2 --check > $O/bench_resnet18_3d_b4.json 2> /dev/null
 python - <<PY
 import json
 for f in ("bench_plain", "bench_20_5", "bench_nvsmall_half2_b8", "bench_resnet18_3d_b4"):

@@ -4,7 +4,7 @@ cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out/${1:-r06_short}; mkdir -p $O
 for rep in 1 2 3 4; do
 for C in 6 3 2 7; do
-  python bench.py --gpus 1 --steps 20 --warmup 5 --contexts $C --no-secondary --no-cpu-baseline 2>/dev/null | python -c "
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 --contexts $C --no-secondary --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('steps 20 contexts $C', round(d['value'],1), d['ms_per_step'], d.get('latency_ms_per_pair'))" | tee -a $O/run.txt
 done
