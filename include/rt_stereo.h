@@ -186,6 +186,41 @@ int rt_disparity_scale(const void* disp_f32, void* out_f32, int64_t n, float sca
  * normalised output of ResNet-18 2D), sample_app/main.cpp:324-330. */
 int rt_disparity_to_u16(const void* disp_f32, void* out_u16, int64_t n, float scale, rtStream stream);
 
+/* ---- left-right consistency check (no counterpart in the reference) --------------------------- */
+/* A left-referenced network gives the right view's disparity when it is fed the mirrored right image as "left" and the mirrored left
+ * image as "right": its output, mirrored back, is referenced to the right view.  The two calls below are the front and the back end of
+ * that second pass as the second half of one batch (rt_stereo_net.h: rt_net_execute_frames_lr ties them to an engine).
+ *
+ * As rt_preprocess_frames_u8 for images [0, batch) of left_dst / right_dst, which here hold 2 * batch images each; bit-identical to it.
+ * Images [batch, 2 * batch) are the mirrored, swapped pair:  left_dst[batch + n] (c, y, x) = right_dst[n](c, y, W-1-x)
+ *                                                             right_dst[batch + n](c, y, x) = left_dst[n] (c, y, W-1-x)
+ * (the mirror of the pre-processed planes, not the planes of the mirrored frame: each value is computed once and stored twice).
+ * Same limits and refusals as rt_preprocess_frames_u8, found before anything is written. */
+int rt_preprocess_frames_u8_lr(const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step, int encoding,
+                               void* left_dst, void* right_dst, int dst_h, int dst_w, int batch, rtStream stream);
+/* Forms of a disparity output (rt_lr_consistency; rt_stereo_net.h: rt_net_execute_frames), for a model whose pixel scale is `scale`:
+ *   RT_DISP_NET         fp32, the network's value        RT_DISP_PIXELS_F32  fp32, value * scale
+ *   RT_DISP_KITTI_U16   uint16, rt_disparity_to_u16(value, 256 * scale) */
+enum { RT_DISP_NET = 0, RT_DISP_PIXELS_F32 = 1, RT_DISP_KITTI_U16 = 2 };
+/* The check, the mask and the output encoding in one launch.
+ * net_disp:    (2 * batch, 1, H, W) fp32 as the engine wrote it for the batch of rt_preprocess_frames_u8_lr
+ * out:         (batch, 1, H, W) in out_kind, invalid pixels = 0
+ * mask_u8:     (batch, 1, H, W) uint8, 255 = consistent, 0 = not; may be NULL
+ * right_out:   (batch, 1, H, W) the right view's disparity, un-mirrored and unmasked, in out_kind; may be NULL
+ * valid_count: device array of `batch` uint64, number of consistent pixels per image; may be NULL
+ * All in fp32, every operation rounded on its own (nothing is contracted into an FMA):
+ *   dL(x) = net_disp[n, 0, y, x] * scale                     left view, pixels
+ *   dR(x) = net_disp[batch + n, 0, y, W-1-x] * scale         right view, pixels, un-mirrored
+ *   xr    = rintf((float)x - dL(x))                          nearest column in the right view, ties to even
+ *   valid = 0 <= xr <= W-1  and  fabsf(dL(x) - dR(xr)) <= max_diff_px        (a NaN anywhere: not valid)
+ * `scale` is the model's pixel scale (width for ResNet-18 2D, 1 for the 3-D models) for every out_kind: the check is always done in
+ * pixels.  A valid pixel of RT_DISP_KITTI_U16 that encodes to 0 is raised to 1 (the KITTI devkit's rule), so that 0 always and only
+ * means "no value" there; for the fp32 kinds, where 0 can be a value, the mask is the authority.  right_out is not masked and not raised.
+ * The outputs must not overlap net_disp.  max_diff_px < 0 or NaN, an unknown kind, batch / H / W < 1, a null net_disp or out: error,
+ * nothing written. */
+int rt_lr_consistency(const void* net_disp, int batch, int H, int W, float scale, float max_diff_px, void* out, int out_kind,
+                      void* mask_u8, void* right_out, void* valid_count, rtStream stream);
+
 /* ---- convolutions (MFMA implicit GEMM) ----------------------------------------------------- */
 /* A plan owns the device copy of the (re-packed) weights, bias and gather tables of one layer,
  * like Conv3DPlugin::configure owns kernel_weights_d_ (lib/conv3d_plugin.cpp:122-133). */

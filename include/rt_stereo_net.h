@@ -72,7 +72,7 @@ int rt_net_execute(rtStereoNet* net, const void* left, const void* right, void* 
  *   RT_DISP_PIXELS_F32  fp32 disparity in pixels: the ROS node's 32FC1 output (stereo_dnn_ros_node.cpp:81, 89); the sample app's
  *                       scale per model (sample_app/main.cpp:325-327): x width for ResNet-18 2D, x 1 for NVSmall / NVTiny / ResNet-18 3D
  *   RT_DISP_KITTI_U16   uint16, the sample app's 16-bit PNG values (main.cpp:321-330): rt_disparity_to_u16(disp, 256 x that scale) */
-enum { RT_DISP_NET = 0, RT_DISP_PIXELS_F32 = 1, RT_DISP_KITTI_U16 = 2 };
+/* (the enum itself is in rt_stereo.h, beside rt_lr_consistency, which writes the same three forms) */
 /* The ROS node's per-frame path (stereo_dnn_ros_node.cpp:60-103) in one call: left_u8 / right_u8 are device batches of camera frames
  * (rt_stereo.h: rt_preprocess_frames_u8 -- src_h x src_w pixels, rows src_step bytes apart, RT_ENC_* encoding), pre-processed to the
  * network's size into fp32 buffers the net owns, run as rt_net_execute does into a disparity the net owns, then written to `disp` as
@@ -82,6 +82,18 @@ enum { RT_DISP_NET = 0, RT_DISP_PIXELS_F32 = 1, RT_DISP_KITTI_U16 = 2 };
  * net are ordered by the caller.  Errors (batch > max_batch, unknown kind or encoding, unsupported scale factors) write nothing. */
 int rt_net_execute_frames(rtStereoNet* net, const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step,
                           int encoding, void* disp, int disp_kind, int batch, rtStream stream);
+/* rt_net_execute_frames plus a left-right consistency check (rt_stereo.h: rt_preprocess_frames_u8_lr, rt_lr_consistency, where the check
+ * is defined): the frames are pre-processed once into the net-owned inputs together with their mirrored, swapped twins, the engine runs
+ * ONE pass at batch 2 * batch (so 2 * batch <= max_batch is required), and rt_lr_consistency writes the caller's buffers:
+ *   disp        (batch,1,H,W) in disp_kind, inconsistent pixels = 0 (RT_DISP_KITTI_U16: a consistent 0 is raised to 1, the KITTI rule)
+ *   mask_u8     (batch,1,H,W) uint8, 255 = consistent; or NULL        disp_right  the right view's disparity in disp_kind; or NULL
+ *   valid_count `batch` uint64 on the device, consistent pixels per image; or NULL
+ * max_diff_px >= 0 is the largest |dL - dR| in pixels that counts as consistent (OpenCV's disp12MaxDiff).  The cost is the engine pass
+ * at twice the batch.  The bindings are those of rt_net_execute_frames: in graph mode a net may alternate between the two calls, each
+ * engine batch keeps its own graph.  Streams, synchronisation and errors (which write nothing) as rt_net_execute_frames. */
+int rt_net_execute_frames_lr(rtStereoNet* net, const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step,
+                             int encoding, void* disp, int disp_kind, void* mask_u8, void* disp_right, void* valid_count,
+                             float max_diff_px, int batch, rtStream stream);
 
 /* Per-launch timing through nvinfer1::IProfiler (single stream, one event pair per launch):
  * writes "name<TAB>milliseconds\n" lines into buf.  Returns 0 or an error. */

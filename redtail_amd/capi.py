@@ -92,6 +92,9 @@ KERNEL_SYMBOLS = {
     "rt_preprocess_frames_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                         c_void_p]),
     "rt_disparity_scale": (c_int, [c_void_p, c_void_p, c_int64, ctypes.c_float, c_void_p]),
+    "rt_preprocess_frames_u8_lr": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                           c_void_p]),
+    "rt_lr_consistency": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rt_conv_plan_input_limit": (c_int, [c_void_p, POINTER(c_float)]),
     "rt_has_experimental": (c_int, []),
     "rt_graph_begin_capture": (c_int, [c_void_p]),
@@ -210,6 +213,19 @@ class KernelLib:
 
     def disparity_scale(self, disp, out, n, scale, stream=None):
         self.check(self.lib.rt_disparity_scale(_ptr(disp), _ptr(out), n, scale, stream), "rt_disparity_scale")
+
+    def preprocess_frames_u8_lr(self, left, right, src_h, src_w, src_step, encoding, left_dst, right_dst, dst_h, dst_w, batch=1,
+                                stream=None):
+        """preprocess_frames_u8 into images [0, batch) of two (2N,3,dst_h,dst_w) batches, plus the mirrored, swapped pair as [batch, 2N)"""
+        self.check(self.lib.rt_preprocess_frames_u8_lr(_ptr(left), _ptr(right), src_h, src_w, src_step, encoding, _ptr(left_dst),
+                                                       _ptr(right_dst), dst_h, dst_w, batch, stream), "rt_preprocess_frames_u8_lr")
+
+    def lr_consistency(self, net_disp, batch, h, w, scale, max_diff_px, out, kind=1, mask=None, right_out=None, valid_count=None,
+                       stream=None):
+        """left-right check of a (2N,1,h,w) engine output of the batch above: (N,1,h,w) `out` in `kind` (RT_DISP_*: 0 raw, 1 pixels,
+        2 KITTI uint16) with inconsistent pixels 0, uint8 mask (255 = consistent), right view's disparity, uint64 count per image"""
+        self.check(self.lib.rt_lr_consistency(_ptr(net_disp), batch, h, w, scale, max_diff_px, _ptr(out), kind, _ptr(mask),
+                                              _ptr(right_out), _ptr(valid_count), stream), "rt_lr_consistency")
 
     def corr_softargmax_pitched(self, l, r, out, batch, C, H, W, D, is_min, in_pitch, out_pitch, out_bstride=0,
                                 dtype=RT_F32, stream=None):
@@ -384,6 +400,8 @@ NET_SYMBOLS = {
     "rt_net_create_from_plan": (c_int, [POINTER(c_void_p), c_void_p, c_size_t]),
     "rt_net_execute": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "rt_net_execute_frames": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "rt_net_execute_frames_lr": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_float, c_int, c_void_p]),
     "rt_net_profile": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_char_p, c_size_t]),
     "rt_net_num_layers": (c_int, [c_void_p]),
     "rt_net_num_launches": (c_int, [c_void_p]),
@@ -533,14 +551,13 @@ class StereoNet:
         self.netlib.check(self.netlib.lib.rt_net_execute(self.handle, _ptr(left), _ptr(right), _ptr(disp), batch, stream),
                           "rt_net_execute")
 
-    def execute_frames(self, left_u8, right_u8, encoding, disp, kind=RT_DISP_PIXELS_F32, batch=1, stream=None, src_step=None,
-                       src_w=None):
-        """rt_net_execute_frames: two batches of camera frames in, disparity out.  Frames are uint8 torch device tensors (numpy arrays under
-        the emulator) of shape (N, H, W, C) -- dense, or a view of padded rows (the row stride is the step) -- or (N, H, step) raw rows, for
-        which src_w gives the width in pixels.  kind: RT_DISP_NET / RT_DISP_PIXELS_F32 (fp32, (N,1,h,w)) or RT_DISP_KITTI_U16 (16-bit)."""
+    @staticmethod
+    def _frame_geometry(what, left_u8, right_u8, encoding, batch, src_step, src_w):
+        """(height, width, step) of a pair of frame batches: (N, H, W, C) -- dense, or a view of padded rows (the row stride is the step) --
+        or (N, H, step) raw rows, for which src_w gives the width in pixels"""
         bpp = ENC_BYTES.get(encoding)
         if bpp is None:                              # the C entry refuses it too; the shape logic below needs the pixel size
-            raise RtError("rt_net_execute_frames: unknown encoding %r" % (encoding,))
+            raise RtError("%s: unknown encoding %r" % (what, encoding))
         shapes = []
         for f in (left_u8, right_u8):
             shape = tuple(f.shape)
@@ -561,9 +578,26 @@ class StereoNet:
         if shapes[0] != shapes[1]:
             raise ValueError("left and right frames differ in size or step: %r vs %r" % tuple(shapes))
         h, w, step = shapes[0]
-        step = step if src_step is None else src_step
+        return h, w, step if src_step is None else src_step
+
+    def execute_frames(self, left_u8, right_u8, encoding, disp, kind=RT_DISP_PIXELS_F32, batch=1, stream=None, src_step=None,
+                       src_w=None):
+        """rt_net_execute_frames: two batches of camera frames in, disparity out.  Frames are uint8 torch device tensors (numpy arrays under
+        the emulator) of shape (N, H, W, C) -- dense, or a view of padded rows (the row stride is the step) -- or (N, H, step) raw rows, for
+        which src_w gives the width in pixels.  kind: RT_DISP_NET / RT_DISP_PIXELS_F32 (fp32, (N,1,h,w)) or RT_DISP_KITTI_U16 (16-bit)."""
+        h, w, step = self._frame_geometry("rt_net_execute_frames", left_u8, right_u8, encoding, batch, src_step, src_w)
         self.netlib.check(self.netlib.lib.rt_net_execute_frames(self.handle, _ptr(left_u8), _ptr(right_u8), h, w, step, encoding,
                                                                 _ptr(disp), kind, batch, stream), "rt_net_execute_frames")
+
+    def execute_frames_lr(self, left_u8, right_u8, encoding, disp, kind=RT_DISP_PIXELS_F32, mask=None, disp_right=None, valid_count=None,
+                          max_diff_px=1.0, batch=1, stream=None, src_step=None, src_w=None):
+        """rt_net_execute_frames_lr: execute_frames with a left-right consistency check (one engine pass at batch 2 * batch, which must
+        fit max_batch).  disp: (N,1,h,w) in `kind`, inconsistent pixels 0; mask: uint8 (N,1,h,w), 255 = consistent; disp_right: the right
+        view's disparity in `kind`; valid_count: N uint64 on the device (torch: int64).  Frames as for execute_frames."""
+        h, w, step = self._frame_geometry("rt_net_execute_frames_lr", left_u8, right_u8, encoding, batch, src_step, src_w)
+        self.netlib.check(self.netlib.lib.rt_net_execute_frames_lr(self.handle, _ptr(left_u8), _ptr(right_u8), h, w, step, encoding,
+                                                                   _ptr(disp), kind, _ptr(mask), _ptr(disp_right), _ptr(valid_count),
+                                                                   max_diff_px, batch, stream), "rt_net_execute_frames_lr")
 
     def set_debug(self, on=True):
         """IExecutionContext::setDebugSync: synchronise every launch and range-check the input of every fp16-pipe convolution"""

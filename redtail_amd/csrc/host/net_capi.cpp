@@ -325,6 +325,39 @@ extern "C" int rt_net_execute_frames(rtStereoNet* net, const void* left_u8, cons
     return 0;
 }
 
+// rt_net_execute_frames with a left-right consistency check: the mirrored, swapped pair rides as the second half of one engine batch.
+// Same three bindings as rt_net_execute_frames (the buffers are sized for max_batch there, and 2 * batch <= max_batch here), so the
+// engine's graph for batch 2b lives beside the one rt_net_execute_frames made for batch b.
+extern "C" int rt_net_execute_frames_lr(rtStereoNet* net, const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step,
+                                        int encoding, void* disp, int disp_kind, void* mask_u8, void* disp_right, void* valid_count,
+                                        float max_diff_px, int batch, rtStream stream) {
+    if (!net || !net->context || !left_u8 || !right_u8 || !disp) return fail("rt_net_execute_frames_lr: null pointer");
+    if (batch < 1 || 2 * (int64_t)batch > net->max_batch)
+        return fail("rt_net_execute_frames_lr: batch " + std::to_string(batch) + " needs an engine batch of " + std::to_string(2 * (int64_t)batch) +
+                    ", max_batch is " + std::to_string(net->max_batch));
+    if (disp_kind != RT_DISP_NET && disp_kind != RT_DISP_PIXELS_F32 && disp_kind != RT_DISP_KITTI_U16)
+        return fail("rt_net_execute_frames_lr: unknown disp_kind " + std::to_string(disp_kind));
+    if (encoding < RT_ENC_BGR8 || encoding > RT_ENC_RGBA8) return fail("rt_net_execute_frames_lr: unknown encoding " + std::to_string(encoding));
+    if (!(max_diff_px >= 0.f)) return fail("rt_net_execute_frames_lr: max_diff_px must be a number >= 0");
+    const int64_t pixels = (int64_t)net->height * net->width;
+    for (void** p : {&net->frame_in[0], &net->frame_in[1], &net->frame_disp}) {
+        const size_t bytes = (size_t)net->max_batch * pixels * (p == &net->frame_disp ? 1 : 3) * sizeof(float);
+        if (!*p && rt_malloc(p, bytes) != 0) return fail(std::string("rt_net_execute_frames_lr: ") + rt_last_error_string());
+    }
+    if (rt_preprocess_frames_u8_lr(left_u8, right_u8, src_h, src_w, src_step, encoding, net->frame_in[0], net->frame_in[1], net->height,
+                                   net->width, batch, stream) != 0)
+        return fail(std::string("rt_net_execute_frames_lr: ") + rt_last_error_string());
+    void* bindings[3] = {net->frame_in[0], net->frame_in[1], net->frame_disp};
+    const bool ok = stream ? net->context->enqueue(2 * batch, bindings, (cudaStream_t)stream, nullptr) : net->context->execute(2 * batch, bindings);
+    if (!ok) return fail("rt_net_execute_frames_lr: " + net->log.last_error);
+    const float scale = net->model == RT_MODEL_RESNET18_2D ? (float)net->width : 1.f;       // as rt_net_execute_frames
+    int rc = rt_lr_consistency(net->frame_disp, batch, net->height, net->width, scale, max_diff_px, disp, disp_kind, mask_u8, disp_right,
+                               valid_count, stream);
+    if (rc == 0 && !stream) rc = rt_stream_sync(nullptr);
+    if (rc != 0) return fail(std::string("rt_net_execute_frames_lr: ") + rt_last_error_string());
+    return 0;
+}
+
 extern "C" int rt_net_profile(rtStereoNet* net, const void* left, const void* right, void* disp, int batch, char* buf,
                               size_t buf_bytes) {
     if (!net || !buf || !buf_bytes) return fail("rt_net_profile: null pointer");

@@ -132,6 +132,204 @@ preprocess_frames_kernel(const unsigned char* __restrict__ left, const unsigned 
     d[2 * plane + o] = b / 255.f;
 }
 
+// The pair batch of preprocess_frames_kernel plus its mirrored, swapped twin for the left-right consistency check: dleft / dright hold
+// 2 * batch images, images [0, batch) are what preprocess_frames_kernel writes (same taps, same accumulation order: bit-identical) and
+//   dleft[batch + n](c, y, x) = dright[n](c, y, dw-1-x),   dright[batch + n](c, y, x) = dleft[n](c, y, dw-1-x)
+// so that the engine's output for image batch + n, mirrored, is the disparity of the right view.  Every value is computed once and stored
+// twice; the u8 frames are read once.  The mirrored copy of a wave's 64 columns [c0, c0+63] is the span [dw-64-c0, dw-1-c0], again 256
+// contiguous bytes.  The values are reversed across the wave in registers (lane l takes lane 63-l's), so lane l stores column
+// dw-64-c0+l: consecutive lanes write consecutive addresses, exactly as in the forward store, instead of walking the span backwards.
+// Lanes past the row's end stay in the wave until the exchange is done (they hold nothing and store nothing).
+// grid = (ceil(dw/64), ceil(dh/4), 2 * batch): z < batch -> left frame z, else right frame z - batch
+template <int BPP, bool DWORD>
+__global__ void __launch_bounds__(256)
+preprocess_frames_lr_kernel(const unsigned char* __restrict__ left, const unsigned char* __restrict__ right, int sh, int sw, int64_t step,
+                            bool rgb_order, float* __restrict__ dleft, float* __restrict__ dright, int dh, int dw, int batch) {
+    __shared__ float s_wx[kAreaMaxTaps][kFramesCols];
+    __shared__ float s_wy[kFramesRows][kAreaMaxTaps];
+    __shared__ int s_x0[kFramesCols], s_y0[kFramesRows];
+    const int tx = threadIdx.x % kFramesCols, ty = threadIdx.x / kFramesCols;
+    const int dx = blockIdx.x * kFramesCols + tx, dy = blockIdx.y * kFramesRows + ty;
+    const bool second = (int)blockIdx.z >= batch;
+    const int n = second ? blockIdx.z - batch : blockIdx.z;
+    const unsigned char* s = (second ? right : left) + (int64_t)n * sh * step;
+    const int64_t plane = (int64_t)dh * dw;
+    float* d = (second ? dright : dleft) + (int64_t)n * 3 * plane;
+    float* m = (second ? dleft : dright) + (int64_t)(batch + n) * 3 * plane;       // the mirrored copy goes to the other side
+    const bool resize = !(sh == dh && sw == dw);
+    if (resize) {                                      // (uniform over the grid: every thread reaches the barrier or none does)
+        if (ty == 0 && dx < dw) {
+            float wx[kAreaMaxTaps];
+            s_x0[tx] = area_taps(dx, (double)sw / dw, sw, wx);
+            for (int i = 0; i < kAreaMaxTaps; i++) s_wx[i][tx] = wx[i];
+        } else if (ty == 1 && tx < kFramesRows && (int)blockIdx.y * kFramesRows + tx < dh) {
+            s_y0[tx] = area_taps(blockIdx.y * kFramesRows + tx, (double)sh / dh, sh, s_wy[tx]);
+        }
+        __syncthreads();
+    }
+    if (dy >= dh) return;                              // a whole wave: ty is the wave index
+    auto pixel = [&](const unsigned char* px, unsigned& c0, unsigned& c1, unsigned& c2) {
+        if constexpr (DWORD) {
+            const unsigned v = *reinterpret_cast<const unsigned*>(px);
+            c0 = v & 0xffu; c1 = (v >> 8) & 0xffu; c2 = (v >> 16) & 0xffu;
+        } else {
+            c0 = px[0]; c1 = px[1]; c2 = px[2];
+        }
+    };
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;               // channels in memory order: B,G,R or R,G,B
+    if (dx < dw) {
+        if (!resize) {
+            unsigned c0, c1, c2;
+            pixel(s + (int64_t)dy * step + (int64_t)dx * BPP, c0, c1, c2);
+            a0 = c0; a1 = c1; a2 = c2;
+        } else {
+            float wx[kAreaMaxTaps], wy[kAreaMaxTaps];
+            for (int i = 0; i < kAreaMaxTaps; i++) { wx[i] = s_wx[i][tx]; wy[i] = s_wy[ty][i]; }
+            const int x0 = s_x0[tx], y0 = s_y0[ty];
+            for (int j = 0; j < kAreaMaxTaps; j++) {
+                if (wy[j] == 0.f) continue;
+                const unsigned char* row = s + (int64_t)(y0 + j) * step;
+                float r0 = 0.f, r1 = 0.f, r2 = 0.f;
+                for (int i = 0; i < kAreaMaxTaps; i++) {
+                    if (wx[i] == 0.f) continue;
+                    unsigned c0, c1, c2;
+                    pixel(row + (x0 + i) * BPP, c0, c1, c2);
+                    r0 += wx[i] * c0; r1 += wx[i] * c1; r2 += wx[i] * c2;
+                }
+                a0 += wy[j] * r0; a1 += wy[j] * r1; a2 += wy[j] * r2;
+            }
+        }
+    }
+    const float r = (rgb_order ? a0 : a2) / 255.f, g = a1 / 255.f, b = (rgb_order ? a2 : a0) / 255.f;
+    const int64_t o = (int64_t)dy * dw + dx;
+    if (dx < dw) {
+        d[o] = r;                     // RGB planes
+        d[plane + o] = g;
+        d[2 * plane + o] = b;
+    }
+    const float mr = __shfl(r, kFramesCols - 1 - tx), mg = __shfl(g, kFramesCols - 1 - tx), mb = __shfl(b, kFramesCols - 1 - tx);
+    const int mx = dw - kFramesCols - (int)blockIdx.x * kFramesCols + tx;      // = dw-1 - (column of lane 63-tx); < 0: that lane is past the row
+    if (mx >= 0) {
+        const int64_t mo = (int64_t)dy * dw + mx;
+        m[mo] = mr;
+        m[plane + mo] = mg;
+        m[2 * plane + mo] = mb;
+    }
+}
+
+// Left-right consistency check, mask and output encoding of a (2 * batch, 1, H, W) engine output whose images [batch, 2 batch) are the
+// mirrored right views (preprocess_frames_lr_kernel).  All in fp32, every operation rounded on its own (contraction is off in this body):
+//   dL(x) = L[y][x] * scale,  dR(x) = R[y][W-1-x] * scale,  xr = rintf((float)x - dL(x)),
+//   valid = 0 <= xr <= W-1 and |dL(x) - dR(xr)| <= max_diff          (a NaN anywhere fails a comparison: not valid)
+// A lane owns 4 consecutive pixels of one image's H*W plane, addressed as a flat run: rows of odd width make every row start at another
+// alignment, a flat run of the plane has one alignment only.  Groups are laid so that their global element index is a multiple of 4
+// (`vec`: all base pointers are 16-byte aligned): an image whose plane starts `a` elements past such a boundary gets a head group of
+// 4 - a and a tail group of what is left, both done element by element by the lanes that own them; every other group is one 16-byte load
+// of L, one 16-byte (fp32) / 8-byte (u16) store per output and one 4-byte mask store.  A group may cross from one row into the next: row
+// and column are carried per element.  The right view's own pixels (right_out only) are one 16-byte load when the group lies in one row;
+// the gather dR(xr) stays inside the row, at most the disparity range away from the lane's own columns: it is served by the caches.
+// valid_count (zeroed by the host entry): a ballot per element slot, then one atomic per wave from its first lane.
+// KIND: 0 raw network value, 1 pixels, 2 KITTI 16-bit (rintf(net * scale16) saturated; a valid 0 is raised to 1, an invalid pixel is 0)
+// grid = (ceil(G / 256), batch) with G = (H*W + 6) / 4 groups: room for the head group
+template <int KIND> struct LrOut { using type = float; };
+template <> struct LrOut<2> { using type = unsigned short; };
+
+template <int KIND>
+__device__ static __forceinline__ typename LrOut<KIND>::type lr_encode(float net, float px, float scale16) {
+    if constexpr (KIND == 0) return net;
+    else if constexpr (KIND == 1) return px;
+    else {
+        const float v = rintf(net * scale16);         // as disparity_u16_kernel
+        return (unsigned short)(v < 0.f ? 0.f : (v > 65535.f ? 65535.f : v));
+    }
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(256)
+lr_consistency_kernel(const float* __restrict__ net, int batch, int H, int W, float scale, float scale16, float max_diff,
+                      void* __restrict__ out_v, unsigned char* __restrict__ mask, void* __restrict__ rout_v,
+                      unsigned long long* __restrict__ count, int vec) {
+#pragma clang fp contract(off)
+    using T = typename LrOut<KIND>::type;
+    const int n = blockIdx.y;
+    const int64_t plane = (int64_t)H * W;
+    const int64_t lbase = (int64_t)n * plane;
+    const float* L = net + lbase;
+    const float* R = net + (int64_t)(batch + n) * plane;
+    T* out = static_cast<T*>(out_v) + lbase;
+    T* rout = rout_v ? static_cast<T*>(rout_v) + lbase : nullptr;
+    if (mask) mask += lbase;
+    const int a = vec ? (int)(lbase & 3) : 0;
+    const int64_t e0 = 4 * ((int64_t)blockIdx.x * 256 + threadIdx.x) - a;      // first element of the group, image-local (< 0 in the head group)
+    const int lo = e0 < 0 ? (int)-e0 : 0;
+    const int hi = e0 + 4 <= plane ? 4 : (int)(plane - e0);                    // <= 0: no element (lanes past the plane still vote below)
+    const bool full = vec && lo == 0 && hi == 4;
+    int y = 0, x = 0;
+    if (lo < hi) {
+        y = (int)((e0 + lo) / W);
+        x = (int)((e0 + lo) - (int64_t)y * W);
+    }
+    float lv[4] = {0.f, 0.f, 0.f, 0.f}, rv[4] = {0.f, 0.f, 0.f, 0.f};
+    if (full) {
+        const float4 v = *reinterpret_cast<const float4*>(L + e0);
+        lv[0] = v.x; lv[1] = v.y; lv[2] = v.z; lv[3] = v.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (k >= lo && k < hi) lv[k] = L[e0 + k];
+    }
+    const bool one_row = full && x + 3 < W;
+    if (rout && one_row) {                             // the right view's pixels x .. x+3 lie mirrored at W-4-x .. W-1-x (4-byte aligned only)
+        float4 v;
+        __builtin_memcpy(&v, R + (int64_t)y * W + (W - 4 - x), sizeof(v));
+        rv[0] = v.w; rv[1] = v.z; rv[2] = v.y; rv[3] = v.x;
+    }
+    T ov[4], rov[4];
+    unsigned ok[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const bool in = k >= lo && k < hi;
+        const float dl = lv[k] * scale;
+        const float xr = rintf((float)x - dl);
+        bool valid = false;
+        if (in && xr >= 0.f && xr <= (float)(W - 1)) {
+            const float dr = R[(int64_t)y * W + (W - 1 - (int)xr)] * scale;
+            valid = fabsf(dl - dr) <= max_diff;
+        }
+        if (rout && in && !one_row) rv[k] = R[(int64_t)y * W + (W - 1 - x)];
+        T o = lr_encode<KIND>(lv[k], dl, scale16);
+        if constexpr (KIND == 2) o = o == 0 ? (T)1 : o;
+        ov[k] = valid ? o : (T)0;
+        rov[k] = lr_encode<KIND>(rv[k], rv[k] * scale, scale16);
+        ok[k] = valid ? 1u : 0u;
+        if (in && ++x == W) { x = 0; y++; }
+    }
+    if (full) {
+        if constexpr (KIND == 2) {
+            *reinterpret_cast<uint2*>(out + e0) = make_uint2((unsigned)ov[0] | ((unsigned)ov[1] << 16), (unsigned)ov[2] | ((unsigned)ov[3] << 16));
+            if (rout) *reinterpret_cast<uint2*>(rout + e0) = make_uint2((unsigned)rov[0] | ((unsigned)rov[1] << 16), (unsigned)rov[2] | ((unsigned)rov[3] << 16));
+        } else {
+            *reinterpret_cast<float4*>(out + e0) = make_float4(ov[0], ov[1], ov[2], ov[3]);
+            if (rout) *reinterpret_cast<float4*>(rout + e0) = make_float4(rov[0], rov[1], rov[2], rov[3]);
+        }
+        if (mask) *reinterpret_cast<unsigned*>(mask + e0) = (ok[0] | (ok[1] << 8) | (ok[2] << 16) | (ok[3] << 24)) * 255u;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (k < lo || k >= hi) continue;
+            out[e0 + k] = ov[k];
+            if (rout) rout[e0 + k] = rov[k];
+            if (mask) mask[e0 + k] = (unsigned char)(ok[k] * 255u);
+        }
+    }
+    if (count) {                                       // (uniform: every lane of every wave is still here)
+        int c = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) c += __builtin_popcountll(__ballot(ok[k]));
+        if ((threadIdx.x & 63) == 0 && c) atomicAdd(count + n, (unsigned long long)c);
+    }
+}
+
 // out = disp * scale (in place allowed): the ROS node's `output *= w` (stereo_dnn_ros_node.cpp:81) on the device
 __global__ void __launch_bounds__(256)
 disparity_scale_kernel(const float* disp, float* out, int64_t n, float scale) {

@@ -633,36 +633,74 @@ extern "C" int rt_preprocess_bgr8(const void* src, int src_h, int src_w, void* d
     return 0;
 }
 
-// (stereo_dnn_ros_node.cpp:42-77): both frames of a pair, any of the node's colour encodings, pitched rows -- one launch
-extern "C" int rt_preprocess_frames_u8(const void* left, const void* right, int src_h, int src_w, int64_t src_step, int encoding,
-                                       void* left_dst, void* right_dst, int dst_h, int dst_w, int batch, rtStream s) {
-    RT_REQUIRE(left && right && left_dst && right_dst, "rt_preprocess_frames_u8: null pointer");
-    RT_REQUIRE(encoding >= RT_ENC_BGR8 && encoding <= RT_ENC_RGBA8, "rt_preprocess_frames_u8: unknown encoding %d", encoding);
-    RT_REQUIRE(src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0 && batch > 0 && batch <= 32767,
-               "rt_preprocess_frames_u8: bad dims");
+// (stereo_dnn_ros_node.cpp:42-77): both frames of a pair, any of the node's colour encodings, pitched rows -- one launch;
+// lr: plus the mirrored, swapped pair as images [batch, 2 batch) of both destinations (preprocess_frames_lr_kernel)
+namespace {
+int preprocess_frames(const char* fn, bool lr, const void* left, const void* right, int src_h, int src_w, int64_t src_step, int encoding,
+                      void* left_dst, void* right_dst, int dst_h, int dst_w, int batch, rtStream s) {
+    RT_REQUIRE(left && right && left_dst && right_dst, "%s: null pointer", fn);
+    RT_REQUIRE(encoding >= RT_ENC_BGR8 && encoding <= RT_ENC_RGBA8, "%s: unknown encoding %d", fn, encoding);
+    RT_REQUIRE(src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0 && batch > 0 && batch <= 32767, "%s: bad dims", fn);
     const int bpp = encoding == RT_ENC_BGRA8 || encoding == RT_ENC_RGBA8 ? 4 : 3;
-    RT_REQUIRE(src_step >= (int64_t)src_w * bpp, "rt_preprocess_frames_u8: row step %lld is shorter than %d pixels of %d bytes",
-               (long long)src_step, src_w, bpp);
+    RT_REQUIRE(src_step >= (int64_t)src_w * bpp, "%s: row step %lld is shorter than %d pixels of %d bytes", fn, (long long)src_step, src_w,
+               bpp);
     if (dst_h > src_h || dst_w > src_w)
-        return fail(RT_E_UNSUPPORTED, "rt_preprocess_frames_u8: INTER_AREA up-scaling (%dx%d -> %dx%d) is not implemented", src_w, src_h, dst_w, dst_h);
+        return fail(RT_E_UNSUPPORTED, "%s: INTER_AREA up-scaling (%dx%d -> %dx%d) is not implemented", fn, src_w, src_h, dst_w, dst_h);
     if ((float)src_w / dst_w > 6.f || (float)src_h / dst_h > 6.f)
-        return fail(RT_E_UNSUPPORTED, "rt_preprocess_frames_u8: scale factors above 6 are not implemented");
+        return fail(RT_E_UNSUPPORTED, "%s: scale factors above 6 are not implemented", fn);
     const bool rgb = encoding == RT_ENC_RGB8 || encoding == RT_ENC_RGBA8;
     const bool aligned = bpp == 4 && ((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right) | (uintptr_t)src_step) & 3) == 0;
     const dim3 grid((unsigned)rt::cdiv(dst_w, rt::kFramesCols), (unsigned)rt::cdiv(dst_h, rt::kFramesRows), (unsigned)(2 * batch));
     const dim3 block(rt::kFramesCols * rt::kFramesRows);
     const unsigned char *l8 = static_cast<const unsigned char*>(left), *r8 = static_cast<const unsigned char*>(right);
     float *lf = static_cast<float*>(left_dst), *rf = static_cast<float*>(right_dst);
-    if (bpp == 3)
-        hipLaunchKernelGGL((rt::preprocess_frames_kernel<3, false>), grid, block, 0, S(s), l8, r8, src_h, src_w, src_step, rgb, lf, rf,
-                           dst_h, dst_w, batch);
-    else if (aligned)
-        hipLaunchKernelGGL((rt::preprocess_frames_kernel<4, true>), grid, block, 0, S(s), l8, r8, src_h, src_w, src_step, rgb, lf, rf,
-                           dst_h, dst_w, batch);
-    else
-        hipLaunchKernelGGL((rt::preprocess_frames_kernel<4, false>), grid, block, 0, S(s), l8, r8, src_h, src_w, src_step, rgb, lf, rf,
-                           dst_h, dst_w, batch);
-    RT_LAUNCH_CHECK("preprocess_frames_kernel");
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, S(s), l8, r8, src_h, src_w, src_step, rgb, lf, rf, dst_h, dst_w, batch);
+    };
+    if (bpp == 3) launch(lr ? rt::preprocess_frames_lr_kernel<3, false> : rt::preprocess_frames_kernel<3, false>);
+    else if (aligned) launch(lr ? rt::preprocess_frames_lr_kernel<4, true> : rt::preprocess_frames_kernel<4, true>);
+    else launch(lr ? rt::preprocess_frames_lr_kernel<4, false> : rt::preprocess_frames_kernel<4, false>);
+    RT_LAUNCH_CHECK(lr ? "preprocess_frames_lr_kernel" : "preprocess_frames_kernel");
+    return 0;
+}
+}  // namespace
+
+extern "C" int rt_preprocess_frames_u8(const void* left, const void* right, int src_h, int src_w, int64_t src_step, int encoding,
+                                       void* left_dst, void* right_dst, int dst_h, int dst_w, int batch, rtStream s) {
+    return preprocess_frames("rt_preprocess_frames_u8", false, left, right, src_h, src_w, src_step, encoding, left_dst, right_dst, dst_h,
+                             dst_w, batch, s);
+}
+
+extern "C" int rt_preprocess_frames_u8_lr(const void* left, const void* right, int src_h, int src_w, int64_t src_step, int encoding,
+                                          void* left_dst, void* right_dst, int dst_h, int dst_w, int batch, rtStream s) {
+    return preprocess_frames("rt_preprocess_frames_u8_lr", true, left, right, src_h, src_w, src_step, encoding, left_dst, right_dst, dst_h,
+                             dst_w, batch, s);
+}
+
+// left-right consistency check + mask + output encoding of a (2 batch, 1, H, W) engine output (lr_consistency_kernel)
+extern "C" int rt_lr_consistency(const void* net_disp, int batch, int H, int W, float scale, float max_diff_px, void* out, int out_kind,
+                                 void* mask_u8, void* right_out, void* valid_count, rtStream s) {
+    RT_REQUIRE(net_disp && out, "rt_lr_consistency: null pointer");
+    RT_REQUIRE(batch >= 1 && batch <= 32767 && H >= 1 && W >= 1 && (int64_t)H * W < ((int64_t)1 << 31), "rt_lr_consistency: bad dims");
+    RT_REQUIRE(max_diff_px >= 0.f, "rt_lr_consistency: max_diff_px must be a number >= 0");       // (false for NaN too)
+    RT_REQUIRE(out_kind == RT_DISP_NET || out_kind == RT_DISP_PIXELS_F32 || out_kind == RT_DISP_KITTI_U16,
+               "rt_lr_consistency: unknown out_kind %d", out_kind);
+    if (valid_count) RT_HIP(hipMemsetAsync(valid_count, 0, (size_t)batch * sizeof(unsigned long long), S(s)));
+    // 16-byte accesses need every base 16-byte aligned (the mask, one byte per pixel: 4); buffers from an allocator are, views may not be
+    const int vec = aligned16(net_disp) && aligned16(out) && (!right_out || aligned16(right_out)) && (reinterpret_cast<uintptr_t>(mask_u8) & 3) == 0;
+    const int64_t groups = ((int64_t)H * W + 3 + 3) / 4;                     // + 3: the head group of an image that starts off a 16-byte boundary
+    const dim3 grid((unsigned)rt::cdiv(groups, 256), (unsigned)batch);
+    const float scale16 = 256.f * scale;
+    const float* in = static_cast<const float*>(net_disp);
+    unsigned char* mask = static_cast<unsigned char*>(mask_u8);
+    unsigned long long* cnt = static_cast<unsigned long long*>(valid_count);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, S(s), in, batch, H, W, scale, scale16, max_diff_px, out, mask, right_out, cnt, vec);
+    };
+    if (out_kind == RT_DISP_NET) launch(rt::lr_consistency_kernel<0>);
+    else if (out_kind == RT_DISP_PIXELS_F32) launch(rt::lr_consistency_kernel<1>);
+    else launch(rt::lr_consistency_kernel<2>);
+    RT_LAUNCH_CHECK("lr_consistency_kernel");
     return 0;
 }
 
