@@ -221,6 +221,34 @@ enum { RT_DISP_NET = 0, RT_DISP_PIXELS_F32 = 1, RT_DISP_KITTI_U16 = 2 };
 int rt_lr_consistency(const void* net_disp, int batch, int H, int W, float scale, float max_diff_px, void* out, int out_kind,
                       void* mask_u8, void* right_out, void* valid_count, rtStream stream);
 
+/* ---- the viz node's debug panel (ros/packages/stereo_dnn_ros_viz/src/stereo_dnn_ros_viz_node.cpp) ---------------------------- */
+/* KITTI colour scheme of the viz node's dispToColor (:49-79): disp_px (n,1,H,W) fp32 pixels -> rgb8, rows dst_step >= 3W bytes apart,
+ * images H * dst_step bytes apart; bytes between 3W and dst_step are not touched.  With the reference's fp32 tables
+ *   weights = {8.77192974, 5.40540552, 8.77192974, 5.74712658, 8.77192974, 5.40540552, 8.77192974, 0}
+ *   cumsum  = {0, 0.114, 0.299, 0.413, 0.587, 0.70100003, 0.88600004, 1},   w_map[i] = (i>>1 & 1, i>>2 & 1, i & 1) as (R, G, B):
+ *   cur   = d / max_disp                                   fp32 division
+ *   index = the largest i in 0..7 with i == 0 or cur > cumsum[i]            (NaN: 0)
+ *   w     = (float)(1.0 - (double)((cur - cumsum[index]) * weights[index]))  subtraction and product in fp32, each rounded on its own
+ *   c     = trunc(clamp((w * w_map[index][c] + (1 - w) * w_map[index+1][c]) * 255, 0, 255))   in double; a map entry of 0 contributes 0
+ * Where the reference is undefined: cur > 1 gives index 7 and w = 1 (also for an infinite cur, where inf * 0 would be NaN), and the
+ * row w_map[8] the reference reads past its table counts as 0: white.  A negative cur makes 1 - w negative, which the reference casts
+ * to uint8_t: here the clamp gives 0.  NaN: black.  max_disp must be a finite number > 0 (the node hard-codes 96). */
+int rt_disparity_to_color(const void* disp_px, int batch, int H, int W, float max_disp, void* dst_rgb8, int64_t dst_step, rtStream stream);
+/* The viz node's whole panel (computeOutput, :81-130) in one launch: per image a (2H) x (2W) rgb8 picture, rows dst_step >= 6W bytes
+ * apart, images 2H * dst_step bytes apart, padding bytes not touched:
+ *   top-left     the left frame, top-right the right frame: RT_ENC_* frames of src_h x src_w pixels, rows src_step bytes apart, as
+ *                rt_preprocess_frames_u8 takes them, area-resized to H x W, in R,G,B order: each channel is rintf (ties to even) of the
+ *                fp32 area average rt_preprocess_frames_u8 forms before its / 255, clamped to [0, 255]; alpha is dropped
+ *   bottom-left  disparity as grey: rintf(d * s) clamped to [0, 255], s = 255.f / max_disp in fp32, NaN -> 0.  (The node's
+ *                `output *= 255.0 / 96` goes through OpenCV's scaled conversion, whose rounding of the factor depends on the version.)
+ *   bottom-right disparity in the KITTI colour scheme: exactly the bytes of rt_disparity_to_color
+ * A disparity of 0 -- what rt_net_execute_frames_lr writes at inconsistent pixels -- is black in both bottom panels.
+ * Limits and refusals as rt_preprocess_frames_u8 (down-scaling or same size, factors <= 6, else RT_E_UNSUPPORTED; a short src_step,
+ * an unknown encoding, null pointers, batch < 1), plus dst_step < 6W and a max_disp that is not a finite number > 0; all found before
+ * anything is written. */
+int rt_viz_mosaic_u8(const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step, int encoding,
+                     const void* disp_px, int H, int W, float max_disp, void* dst_rgb8, int64_t dst_step, int batch, rtStream stream);
+
 /* ---- convolutions (MFMA implicit GEMM) ----------------------------------------------------- */
 /* A plan owns the device copy of the (re-packed) weights, bias and gather tables of one layer,
  * like Conv3DPlugin::configure owns kernel_weights_d_ (lib/conv3d_plugin.cpp:122-133). */

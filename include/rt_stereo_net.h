@@ -94,6 +94,18 @@ int rt_net_execute_frames(rtStereoNet* net, const void* left_u8, const void* rig
 int rt_net_execute_frames_lr(rtStereoNet* net, const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step,
                              int encoding, void* disp, int disp_kind, void* mask_u8, void* disp_right, void* valid_count,
                              float max_diff_px, int batch, rtStream stream);
+/* The DNN node's and the viz node's messages from one call: rt_net_execute_frames(..., RT_DISP_PIXELS_F32) -- or, when max_diff_px >= 0,
+ * rt_net_execute_frames_lr(..., RT_DISP_PIXELS_F32, mask_u8, NULL, valid_count, max_diff_px) -- followed by rt_viz_mosaic_u8
+ * (rt_stereo.h) of the same frames and of the disparity just written, on the same stream: one more launch, no new buffers.
+ *   disp_px   (batch,1,H,W) fp32 disparity in pixels (the DNN node's 32FC1 message)
+ *   viz_rgb8  per image a (2H) x (2W) rgb8 panel, rows viz_step >= 6W bytes apart (the viz node's rgb8 message); max_disp: its colour
+ *             range (the node uses 96).  A checked disparity is 0 at inconsistent pixels, which is black in both disparity panels.
+ * max_diff_px < 0: no check, mask_u8 and valid_count must be NULL; a NaN is an error.  The panel is launched outside the engine's graph,
+ * like the pre-processing and the output step, so in graph mode frame, disparity and panel pointers may rotate.  Streams and
+ * synchronisation as the two calls; every error (theirs, a short viz_step, a max_disp that is not a finite number > 0) writes nothing. */
+int rt_net_execute_frames_viz(rtStereoNet* net, const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step,
+                              int encoding, void* disp_px, void* viz_rgb8, int64_t viz_step, float max_disp, float max_diff_px,
+                              void* mask_u8, void* valid_count, int batch, rtStream stream);
 
 /* Per-launch timing through nvinfer1::IProfiler (single stream, one event pair per launch):
  * writes "name<TAB>milliseconds\n" lines into buf.  Returns 0 or an error. */

@@ -95,6 +95,9 @@ KERNEL_SYMBOLS = {
     "rt_preprocess_frames_u8_lr": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                            c_void_p]),
     "rt_lr_consistency": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rt_disparity_to_color": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p]),
+    "rt_viz_mosaic_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_int64, c_int,
+                                 c_void_p]),
     "rt_conv_plan_input_limit": (c_int, [c_void_p, POINTER(c_float)]),
     "rt_has_experimental": (c_int, []),
     "rt_graph_begin_capture": (c_int, [c_void_p]),
@@ -277,6 +280,18 @@ class KernelLib:
         """the library carries the rejected kernel families (RT_EXPERIMENTAL build: the emulator library of the CPU test tier)"""
         return bool(self.lib.rt_has_experimental())
 
+    def disparity_to_color(self, disp_px, batch, h, w, max_disp, dst_rgb8, dst_step=None, stream=None):
+        """(N,1,h,w) fp32 disparity in pixels -> rgb8 in the KITTI colour scheme, rows dst_step (default 3 w) bytes apart"""
+        self.check(self.lib.rt_disparity_to_color(_ptr(disp_px), batch, h, w, max_disp, _ptr(dst_rgb8), 3 * w if dst_step is None else dst_step,
+                                                  stream), "rt_disparity_to_color")
+
+    def viz_mosaic_u8(self, left, right, src_h, src_w, src_step, encoding, disp_px, h, w, max_disp, dst_rgb8, dst_step=None, batch=1,
+                      stream=None):
+        """the viz node's 2x2 panel: frames as for preprocess_frames_u8 and their (N,1,h,w) disparity in pixels -> per image a 2h x 2w rgb8
+        picture, rows dst_step (default 6 w) bytes apart: left | right over grey disparity | KITTI-coloured disparity"""
+        self.check(self.lib.rt_viz_mosaic_u8(_ptr(left), _ptr(right), src_h, src_w, src_step, encoding, _ptr(disp_px), h, w, max_disp,
+                                             _ptr(dst_rgb8), 6 * w if dst_step is None else dst_step, batch, stream), "rt_viz_mosaic_u8")
+
     def check_range(self, x, rows, valid, pitch, dtype=RT_F32, limit=65504.0, stream=None):
         """(max finite |x|, number of elements with |x| >= limit or non-finite) of a device tensor (rt_check_range)"""
         mx, bad = c_float(), c_int64()
@@ -402,6 +417,8 @@ NET_SYMBOLS = {
     "rt_net_execute_frames": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_void_p]),
     "rt_net_execute_frames_lr": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                          c_void_p, c_float, c_int, c_void_p]),
+    "rt_net_execute_frames_viz": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int64, c_float,
+                                          c_float, c_void_p, c_void_p, c_int, c_void_p]),
     "rt_net_profile": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_char_p, c_size_t]),
     "rt_net_num_layers": (c_int, [c_void_p]),
     "rt_net_num_launches": (c_int, [c_void_p]),
@@ -598,6 +615,17 @@ class StereoNet:
         self.netlib.check(self.netlib.lib.rt_net_execute_frames_lr(self.handle, _ptr(left_u8), _ptr(right_u8), h, w, step, encoding,
                                                                    _ptr(disp), kind, _ptr(mask), _ptr(disp_right), _ptr(valid_count),
                                                                    max_diff_px, batch, stream), "rt_net_execute_frames_lr")
+
+    def execute_frames_viz(self, left_u8, right_u8, encoding, disp_px, viz_rgb8, viz_step=None, max_disp=96.0, max_diff_px=-1.0, mask=None,
+                           valid_count=None, batch=1, stream=None, src_step=None, src_w=None):
+        """rt_net_execute_frames_viz: execute_frames (max_diff_px < 0) or execute_frames_lr (max_diff_px >= 0) with RT_DISP_PIXELS_F32 into
+        disp_px, then the viz node's 2h x 2w rgb8 panel of the same frames and that disparity into viz_rgb8, rows viz_step (default 6 w)
+        bytes apart.  Frames as for execute_frames."""
+        h, w, step = self._frame_geometry("rt_net_execute_frames_viz", left_u8, right_u8, encoding, batch, src_step, src_w)
+        self.netlib.check(self.netlib.lib.rt_net_execute_frames_viz(self.handle, _ptr(left_u8), _ptr(right_u8), h, w, step, encoding,
+                                                                    _ptr(disp_px), _ptr(viz_rgb8), 6 * self.width if viz_step is None else viz_step,
+                                                                    max_disp, max_diff_px, _ptr(mask), _ptr(valid_count), batch, stream),
+                          "rt_net_execute_frames_viz")
 
     def set_debug(self, on=True):
         """IExecutionContext::setDebugSync: synchronise every launch and range-check the input of every fp16-pipe convolution"""

@@ -358,6 +358,30 @@ extern "C" int rt_net_execute_frames_lr(rtStereoNet* net, const void* left_u8, c
     return 0;
 }
 
+// The DNN node's disparity and the viz node's panel (stereo_dnn_ros_viz_node.cpp:81-130) from one call.  What only the panel can refuse
+// is checked first, so that an error writes nothing; everything else is refused by the wrapped call before it launches anything.
+extern "C" int rt_net_execute_frames_viz(rtStereoNet* net, const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step,
+                                         int encoding, void* disp_px, void* viz_rgb8, int64_t viz_step, float max_disp, float max_diff_px,
+                                         void* mask_u8, void* valid_count, int batch, rtStream stream) {
+    if (!net || !net->context || !left_u8 || !right_u8 || !disp_px || !viz_rgb8) return fail("rt_net_execute_frames_viz: null pointer");
+    if (!(max_disp > 0.f && max_disp <= 3.402823466e38f)) return fail("rt_net_execute_frames_viz: max_disp must be a number > 0");
+    if (viz_step < 6 * (int64_t)net->width)
+        return fail("rt_net_execute_frames_viz: viz_step " + std::to_string(viz_step) + " is shorter than " + std::to_string(2 * net->width) +
+                    " pixels of 3 bytes");
+    if (max_diff_px != max_diff_px) return fail("rt_net_execute_frames_viz: max_diff_px is not a number");
+    const bool check = max_diff_px >= 0.f;
+    if (!check && (mask_u8 || valid_count)) return fail("rt_net_execute_frames_viz: mask_u8 and valid_count need a check (max_diff_px >= 0)");
+    const int rc = check ? rt_net_execute_frames_lr(net, left_u8, right_u8, src_h, src_w, src_step, encoding, disp_px, RT_DISP_PIXELS_F32, mask_u8,
+                                                    nullptr, valid_count, max_diff_px, batch, stream)
+                         : rt_net_execute_frames(net, left_u8, right_u8, src_h, src_w, src_step, encoding, disp_px, RT_DISP_PIXELS_F32, batch, stream);
+    if (rc != 0) return rc;                            // (the wrapped call has set the message)
+    int vrc = rt_viz_mosaic_u8(left_u8, right_u8, src_h, src_w, src_step, encoding, disp_px, net->height, net->width, max_disp, viz_rgb8,
+                               viz_step, batch, stream);
+    if (vrc == 0 && !stream) vrc = rt_stream_sync(nullptr);
+    if (vrc != 0) return fail(std::string("rt_net_execute_frames_viz: ") + rt_last_error_string());
+    return 0;
+}
+
 extern "C" int rt_net_profile(rtStereoNet* net, const void* left, const void* right, void* disp, int batch, char* buf,
                               size_t buf_bytes) {
     if (!net || !buf || !buf_bytes) return fail("rt_net_profile: null pointer");

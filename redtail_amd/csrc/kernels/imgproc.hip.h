@@ -330,6 +330,199 @@ lr_consistency_kernel(const float* __restrict__ net, int batch, int H, int W, fl
     }
 }
 
+// The viz node's 2x2 debug panel (reference ros/packages/stereo_dnn_ros_viz/src/stereo_dnn_ros_viz_node.cpp:27-130), rgb8:
+//   top-left  left frame, area-resized      top-right    right frame, area-resized
+//   bottom-left  disparity as grey          bottom-right disparity in the KITTI colour scheme (dispToColor, :49-79)
+// One pixel of a panel packed as R | G << 8 | B << 16.
+__device__ static __forceinline__ unsigned viz_sat_u8(float a) {           // saturate_cast<uchar>(cvRound(a)): nearest even, NaN -> 0
+    const float v = rintf(a);
+    return (unsigned)(v > 0.f ? (v < 255.f ? v : 255.f) : 0.f);
+}
+
+__device__ static __forceinline__ unsigned viz_grey(float d, float s) {    // s = 255.f / max_disp, formed once on the host
+    return viz_sat_u8(d * s) * 0x010101u;
+}
+
+// cur = d / max_disp; index = the last i with cur > cumsum[i] (0 if none, also for NaN); w = (float)(1.0 - (double)((cur - cumsum[index]) *
+// weights[index])), subtraction and product in fp32, each rounded on its own; channel = trunc(clamp((w * m0 + (1 - w) * m1) * 255)) in
+// double, where m0 / m1 are the 0-or-1 entries of the corner colours index and index + 1: an entry of 0 contributes 0 whatever w is.
+// index 7 (cur > 1) has weight 0, so w = 1 there by definition (also for an infinite cur), and the row past the table counts as 0: white.
+__device__ static __forceinline__ unsigned viz_color(float d, float max_disp) {
+#pragma clang fp contract(off)
+    constexpr float weights[8] = {8.77192974f, 5.40540552f, 8.77192974f, 5.74712658f, 8.77192974f, 5.40540552f, 8.77192974f, 0.f};
+    constexpr float cumsum[8] = {0.f, 0.114f, 0.299f, 0.413f, 0.587f, 0.70100003f, 0.88600004f, 1.f};
+    const float cur = d / max_disp;
+    int index = 0;
+    float base = cumsum[0], wgt = weights[0];
+#pragma unroll
+    for (int i = 1; i < 8; i++)
+        if (cur > cumsum[i]) { index = i; base = cumsum[i]; wgt = weights[i]; }
+    const float x = (cur - base) * wgt;
+    const double w = index == 7 ? 1.0 : (double)(float)(1.0 - (double)x);
+    const double u = 1.0 - w;
+    const int next = index == 7 ? 0 : index + 1;                          // w_map[i] = (i >> 1 & 1, i >> 2 & 1, i & 1); "w_map[8]" = 0
+    unsigned px = 0;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const int bit = c == 0 ? 1 : (c == 1 ? 2 : 0);
+        const double v = (((index >> bit) & 1 ? w : 0.0) + ((next >> bit) & 1 ? u : 0.0)) * 255.0;
+        px |= (unsigned)(v > 0.0 ? (v < 255.0 ? v : 255.0) : 0.0) << (8 * c);         // a NaN or a negative value: 0
+    }
+    return px;
+}
+
+// The panel (MOSAIC: rows 2H x 6W bytes) or the colour picture alone (!MOSAIC: H x 3W bytes, left / right unused), one launch.
+// Pixels are 3 bytes, the network widths are odd and dst_step is any number, so neither a pixel nor a panel nor a row starts on a dword.
+// A block is kVizRows picture rows x 63 chunks, a chunk being an ALIGNED 12-byte piece of a row's memory: 252 pixels and the one before
+// and after them, whose bytes complete the first and last chunk when the row starts off a dword.
+//   phase 1: thread t forms the picture pixel 252 * blockIdx.x - 1 + t of each row -- consecutive lanes read consecutive source pixels
+//            / disparities, as preprocess_frames_kernel; same area_taps, tap order and accumulation order, the x taps of the block's
+//            columns and the y taps of its rows built once into LDS -- and leaves it packed in LDS;
+//   phase 2: wave r stores row r: lane l takes the 4 (row on a dword: a = 0 or 3) or 5 packed pixels that overlap its chunk, shifts
+//            them into three dwords and stores those.  Only a chunk cut by the row's first or last byte is stored byte by byte.
+// One row per block: a thread's rows are a serial chain of dependent loads, and at the network's sizes the launch is bound by that chain
+// and by the blocks' start-up (the taps), not by bytes.  Measured, 1257x369 from 1280x720 / 513x257 from 672x376 (profiles/README.md):
+// 4 rows per block 19.0 / 13.6 us, 1 row 19.0 / 9.0 us, 1 row with a pixel's 9 taps loaded at once 17.0 / 7.7 us.
+// The top and the bottom half of the panel are separate blocks (uniform branches).
+// grid = (ceil(chunks / 63), (MOSAIC ? 2 : 1) * ceil(H / kVizRows), batch), chunks = ceil((row bytes + 3) / 12)
+constexpr int kVizChunks = 63, kVizRows = 1, kVizPixels = 4 * kVizChunks + 2;
+static_assert(kVizPixels + kVizRows <= 256 && kVizRows <= 4, "viz_kernel: one thread per column, the last ones build the y taps");
+template <int BPP, bool DWORD, bool MOSAIC>
+__global__ void __launch_bounds__(256)
+viz_kernel(const unsigned char* __restrict__ left, const unsigned char* __restrict__ right, int sh, int sw, int64_t step, bool rgb_order,
+           const float* __restrict__ disp, int H, int W, float max_disp, float grey_scale, unsigned char* __restrict__ dst,
+           int64_t dst_step) {
+    __shared__ float s_wx[kAreaMaxTaps][kVizPixels];
+    __shared__ float s_wy[kVizRows][kAreaMaxTaps];
+    __shared__ int s_x0[kVizPixels], s_y0[kVizRows];
+    __shared__ unsigned s_px[kVizRows][kVizPixels];
+    const int tid = threadIdx.x, n = blockIdx.z;
+    const int yblocks = (H + kVizRows - 1) / kVizRows;
+    const bool top = MOSAIC && (int)blockIdx.y < yblocks;
+    const int y0 = ((int)blockIdx.y - (MOSAIC && !top ? yblocks : 0)) * kVizRows;   // first row of the block within its panel
+    const int npix = MOSAIC ? 2 * W : W;                                            // pixels of a picture row
+    const int p = (int)blockIdx.x * (4 * kVizChunks) - 1 + tid;                     // picture column of this thread's pixels
+    const bool second = p >= W;                                                     // right-hand panel
+    const int col = second ? p - W : p;
+    const bool mine = tid < kVizPixels && p >= 0 && p < npix;
+    if (!mine && tid < kVizPixels)                     // a column outside the picture: its packed value is ORed beside its neighbours' below
+        for (int r = 0; r < kVizRows; r++) s_px[r][tid] = 0u;
+    if (top) {
+        const bool resize = !(sh == H && sw == W);
+        if (resize) {                                  // (uniform over the block: every thread reaches the barrier or none does)
+            if (mine) {
+                float wx[kAreaMaxTaps];
+                s_x0[tid] = area_taps(col, (double)sw / W, sw, wx);
+                for (int i = 0; i < kAreaMaxTaps; i++) s_wx[i][tid] = wx[i];
+            }
+            const int yt = 255 - tid;                  // the block's last threads hold no column (kVizPixels + kVizRows <= 256)
+            if (yt < kVizRows && y0 + yt < H) s_y0[yt] = area_taps(y0 + yt, (double)sh / H, sh, s_wy[yt]);
+            __syncthreads();
+        }
+        if (mine) {
+            const unsigned char* s = (second ? right : left) + (int64_t)n * sh * step;
+            auto pixel = [&](const unsigned char* px, unsigned& c0, unsigned& c1, unsigned& c2) {
+                if constexpr (DWORD) {
+                    const unsigned v = *reinterpret_cast<const unsigned*>(px);
+                    c0 = v & 0xffu; c1 = (v >> 8) & 0xffu; c2 = (v >> 16) & 0xffu;
+                } else {
+                    c0 = px[0]; c1 = px[1]; c2 = px[2];
+                }
+            };
+            float wx[kAreaMaxTaps];
+            int x0 = 0;
+            if (resize) {
+                for (int i = 0; i < kAreaMaxTaps; i++) wx[i] = s_wx[i][tid];
+                x0 = s_x0[tid];
+            }
+            for (int r = 0; r < kVizRows && y0 + r < H; r++) {
+                unsigned c0, c1, c2;                                       // channels in memory order: B,G,R or R,G,B
+                if (!resize) {
+                    pixel(s + (int64_t)(y0 + r) * step + (int64_t)col * BPP, c0, c1, c2);
+                } else if (wx[3] == 0.f && s_wy[r][3] == 0.f) {
+                    // at most 3 taps an axis (every factor up to 2: the network's sizes from the usual cameras): all 9 source pixels
+                    // are loaded before the first is used -- one trip to memory instead of one per source row -- at clamped
+                    // addresses; a tap of weight 0 is skipped as below, so the sums are the same operations in the same order
+                    const int ys = s_y0[r];
+                    unsigned t[3][3][3];
+#pragma unroll
+                    for (int j = 0; j < 3; j++) {
+                        const int yy = ys + j < sh ? ys + j : sh - 1;
+                        const unsigned char* row = s + (int64_t)yy * step;
+#pragma unroll
+                        for (int i = 0; i < 3; i++) {
+                            const int xx = x0 + i < sw ? x0 + i : sw - 1;
+                            pixel(row + xx * BPP, t[j][i][0], t[j][i][1], t[j][i][2]);
+                        }
+                    }
+                    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+#pragma unroll
+                    for (int j = 0; j < 3; j++) {
+                        const float wy = s_wy[r][j];
+                        float r0 = 0.f, r1 = 0.f, r2 = 0.f;
+#pragma unroll
+                        for (int i = 0; i < 3; i++) {
+                            const bool on = wx[i] != 0.f;
+                            r0 = on ? r0 + wx[i] * t[j][i][0] : r0; r1 = on ? r1 + wx[i] * t[j][i][1] : r1; r2 = on ? r2 + wx[i] * t[j][i][2] : r2;
+                        }
+                        const bool on = wy != 0.f;
+                        a0 = on ? a0 + wy * r0 : a0; a1 = on ? a1 + wy * r1 : a1; a2 = on ? a2 + wy * r2 : a2;
+                    }
+                    c0 = viz_sat_u8(a0); c1 = viz_sat_u8(a1); c2 = viz_sat_u8(a2);
+                } else {
+                    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+                    const int ys = s_y0[r];
+                    for (int j = 0; j < kAreaMaxTaps; j++) {
+                        const float wy = s_wy[r][j];
+                        if (wy == 0.f) continue;
+                        const unsigned char* row = s + (int64_t)(ys + j) * step;
+                        float r0 = 0.f, r1 = 0.f, r2 = 0.f;
+                        for (int i = 0; i < kAreaMaxTaps; i++) {
+                            if (wx[i] == 0.f) continue;
+                            unsigned t0, t1, t2;
+                            pixel(row + (x0 + i) * BPP, t0, t1, t2);
+                            r0 += wx[i] * t0; r1 += wx[i] * t1; r2 += wx[i] * t2;
+                        }
+                        a0 += wy * r0; a1 += wy * r1; a2 += wy * r2;
+                    }
+                    c0 = viz_sat_u8(a0); c1 = viz_sat_u8(a1); c2 = viz_sat_u8(a2);
+                }
+                s_px[r][tid] = rgb_order ? (c0 | (c1 << 8) | (c2 << 16)) : (c2 | (c1 << 8) | (c0 << 16));
+            }
+        }
+    } else if (mine) {
+        for (int r = 0; r < kVizRows && y0 + r < H; r++) {
+            const float d = disp[((int64_t)n * H + (y0 + r)) * W + col];
+            s_px[r][tid] = MOSAIC && !second ? viz_grey(d, grey_scale) : viz_color(d, max_disp);
+        }
+    }
+    __syncthreads();
+    const int lane = tid % 64, r = tid / 64, y = y0 + r;
+    if (lane >= kVizChunks || r >= kVizRows || y >= H) return;
+    unsigned char* row = dst + ((int64_t)n * (MOSAIC ? 2 * H : H) + (MOSAIC && !top ? H + y : y)) * dst_step;
+    const int a = (int)(reinterpret_cast<uintptr_t>(row) & 3);                     // the row starts `a` bytes past a dword
+    const int bytes = 3 * npix;
+    const int b0 = 12 * ((int)blockIdx.x * kVizChunks + lane) - a;                 // row byte at which this chunk starts (< 0: the row's head)
+    if (b0 >= bytes) return;
+    // the chunk's bytes are bytes o .. o + 11 of the pixels 4 * chunk - (a > 0) and following; a = 0: +0, 1: +2, 2: +1, 3: +0
+    const int i0 = 4 * lane + (a ? 0 : 1), o = a ? 3 - a : 0;
+    const unsigned q0 = s_px[r][i0], q1 = s_px[r][i0 + 1], q2 = s_px[r][i0 + 2], q3 = s_px[r][i0 + 3];
+    unsigned t[4] = {q0 | (q1 << 24), (q1 >> 8) | (q2 << 16), (q2 >> 16) | (q3 << 8), 0u};
+    if (o) {                                           // (uniform over the wave)
+        t[3] = s_px[r][i0 + 4];
+        for (int i = 0; i < 3; i++) t[i] = (t[i] >> (8 * o)) | (t[i + 1] << (32 - 8 * o));
+    }
+    const int lo = b0 < 0 ? -b0 : 0, hi = bytes - b0 < 12 ? bytes - b0 : 12;      // the bytes [lo, hi) of the chunk belong to the row
+    for (int i = 0; i < 3; i++) {
+        if (4 * i >= lo && 4 * i + 4 <= hi) {
+            *reinterpret_cast<unsigned*>(row + b0 + 4 * i) = t[i];
+        } else {
+            for (int j = 4 * i; j < 4 * i + 4; j++)
+                if (j >= lo && j < hi) row[b0 + j] = (unsigned char)(t[i] >> (8 * (j - 4 * i)));
+        }
+    }
+}
+
 // out = disp * scale (in place allowed): the ROS node's `output *= w` (stereo_dnn_ros_node.cpp:81) on the device
 __global__ void __launch_bounds__(256)
 disparity_scale_kernel(const float* disp, float* out, int64_t n, float scale) {

@@ -704,6 +704,61 @@ extern "C" int rt_lr_consistency(const void* net_disp, int batch, int H, int W, 
     return 0;
 }
 
+// the viz node's panel (stereo_dnn_ros_viz_node.cpp:81-130) and its colour picture alone (:49-79): viz_kernel
+namespace {
+int viz_launch(const char* fn, bool mosaic, const void* left, const void* right, int src_h, int src_w, int64_t src_step, int encoding,
+               const void* disp_px, int H, int W, float max_disp, void* dst, int64_t dst_step, int batch, rtStream s) {
+    RT_REQUIRE(disp_px && dst && (!mosaic || (left && right)), "%s: null pointer", fn);
+    RT_REQUIRE(batch >= 1 && batch <= 32767 && H >= 1 && W >= 1 && 2 * rt::cdiv(H, rt::kVizRows) <= 65535 && W <= (1 << 24) && (int64_t)H * W < ((int64_t)1 << 31),
+               "%s: bad dims", fn);
+    RT_REQUIRE(max_disp > 0.f && max_disp <= 3.402823466e38f,"%s: max_disp must be a number > 0", fn);       // (false for NaN too)
+    RT_REQUIRE(dst_step >= (int64_t)(mosaic ? 6 : 3) * W, "%s: row step %lld is shorter than %d pixels of 3 bytes", fn, (long long)dst_step,
+               (mosaic ? 2 : 1) * W);
+    int bpp = 3;
+    bool rgb = true, aligned = false;
+    if (mosaic) {
+        RT_REQUIRE(encoding >= RT_ENC_BGR8 && encoding <= RT_ENC_RGBA8, "%s: unknown encoding %d", fn, encoding);
+        RT_REQUIRE(src_h > 0 && src_w > 0, "%s: bad dims", fn);
+        bpp = encoding == RT_ENC_BGRA8 || encoding == RT_ENC_RGBA8 ? 4 : 3;
+        RT_REQUIRE(src_step >= (int64_t)src_w * bpp, "%s: row step %lld is shorter than %d pixels of %d bytes", fn, (long long)src_step, src_w,
+                   bpp);
+        if (H > src_h || W > src_w)
+            return fail(RT_E_UNSUPPORTED, "%s: INTER_AREA up-scaling (%dx%d -> %dx%d) is not implemented", fn, src_w, src_h, W, H);
+        if ((float)src_w / W > 6.f || (float)src_h / H > 6.f)
+            return fail(RT_E_UNSUPPORTED, "%s: scale factors above 6 are not implemented", fn);
+        rgb = encoding == RT_ENC_RGB8 || encoding == RT_ENC_RGBA8;
+        aligned = bpp == 4 && ((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right) | (uintptr_t)src_step) & 3) == 0;
+    }
+    const int64_t chunks = ((int64_t)(mosaic ? 6 : 3) * W + 3 + 11) / 12;             // + 3: a row that starts 3 bytes past a dword
+    const int yblocks = (int)rt::cdiv(H, rt::kVizRows);
+    const dim3 grid((unsigned)rt::cdiv(chunks, rt::kVizChunks), (unsigned)(mosaic ? 2 * yblocks : yblocks), (unsigned)batch);
+    const float grey_scale = 255.f / max_disp;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, S(s), static_cast<const unsigned char*>(left), static_cast<const unsigned char*>(right),
+                           src_h, src_w, src_step, rgb, static_cast<const float*>(disp_px), H, W, max_disp, grey_scale,
+                           static_cast<unsigned char*>(dst), dst_step);
+    };
+    if (!mosaic) launch(rt::viz_kernel<3, false, false>);
+    else if (bpp == 3) launch(rt::viz_kernel<3, false, true>);
+    else if (aligned) launch(rt::viz_kernel<4, true, true>);
+    else launch(rt::viz_kernel<4, false, true>);
+    RT_LAUNCH_CHECK("viz_kernel");
+    return 0;
+}
+}  // namespace
+
+extern "C" int rt_disparity_to_color(const void* disp_px, int batch, int H, int W, float max_disp, void* dst_rgb8, int64_t dst_step,
+                                     rtStream s) {
+    return viz_launch("rt_disparity_to_color", false, nullptr, nullptr, H, W, 0, RT_ENC_RGB8, disp_px, H, W, max_disp, dst_rgb8, dst_step,
+                      batch, s);
+}
+
+extern "C" int rt_viz_mosaic_u8(const void* left, const void* right, int src_h, int src_w, int64_t src_step, int encoding,
+                                const void* disp_px, int H, int W, float max_disp, void* dst_rgb8, int64_t dst_step, int batch, rtStream s) {
+    return viz_launch("rt_viz_mosaic_u8", true, left, right, src_h, src_w, src_step, encoding, disp_px, H, W, max_disp, dst_rgb8, dst_step,
+                      batch, s);
+}
+
 extern "C" int rt_disparity_scale(const void* disp, void* out, int64_t n, float scale, rtStream s) {
     RT_REQUIRE(disp && out && n > 0, "rt_disparity_scale: bad arguments");
     hipLaunchKernelGGL(rt::disparity_scale_kernel, dim3((unsigned)rt::cdiv(n, 256)), dim3(256), 0, S(s),
