@@ -221,6 +221,49 @@ enum { RT_DISP_NET = 0, RT_DISP_PIXELS_F32 = 1, RT_DISP_KITTI_U16 = 2 };
 int rt_lr_consistency(const void* net_disp, int batch, int H, int W, float scale, float max_diff_px, void* out, int out_kind,
                       void* mask_u8, void* right_out, void* valid_count, rtStream stream);
 
+/* ---- frames of any size in, disparity at the frame's size out ------------------------------------------------------------------ */
+/* The whole of cv::resize(INTER_AREA) on the fp32 image as the ROS node calls it for whatever the camera sends
+ * (stereo_dnn_ros_node.cpp:42-58), for both frames of a pair batch in one launch.  Arguments as rt_preprocess_frames_u8.
+ *   dst_h <= src_h and dst_w <= src_w: the box filter; bit-identical to rt_preprocess_frames_u8 (the same code).
+ *   otherwise (either axis grows): OpenCV does not mix filters per axis -- "true area interpolation is only implemented for
+ *   scale_x >= 1 && scale_y >= 1; in other cases it is emulated using some variant of bilinear" -- so BOTH axes use the two-tap set-up
+ *   of its area_mode branch, the shrinking one included.  Per axis, source size n, destination size m, destination index d, positions
+ *   in double, the weight cast to fp32:
+ *       inv = (double)m / n;   scale = 1.0 / inv
+ *       s   = (int)floor(d * scale)
+ *       f   = (float)((d + 1) - (s + 1) * inv);   f = f <= 0 ? 0.f : f - floorf(f)
+ *       if (s >= n - 1) { s = n - 1; f = 0.f; }
+ *       taps: source s with weight 1.f - f, source min(s + 1, n - 1) with weight f
+ *   (s + 1) * inv is rounded before the subtraction: nothing in the tap set-up is contracted into an FMA.  Value, per channel, fp32, x
+ *   first, every product and sum rounded on its own:  row_j = S[y_j][x0] * a0 + S[y_j][x1] * a1  for the two rows,
+ *   v = row_0 * b0 + row_1 * b1,  then colour order, / 255.f and planes exactly as rt_preprocess_frames_u8.  A pure integer
+ *   magnification thereby replicates pixels (INTER_AREA's known behaviour); the same size is a copy.
+ * mirror_twin != 0: left_dst / right_dst hold 2 * batch images and images [batch, 2 batch) are the mirrored, swapped pair as
+ * rt_preprocess_frames_u8_lr defines it; in the box case bit-identical to rt_preprocess_frames_u8_lr.
+ * Limits: every axis factor src / dst within [1/6, 6], else RT_E_UNSUPPORTED; a short src_step, an unknown encoding, null pointers,
+ * batch < 1: error.  All found before anything is written. */
+int rt_preprocess_frames_u8_cv(const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step, int encoding,
+                               void* left_dst, void* right_dst, int dst_h, int dst_w, int batch, int mirror_twin, rtStream stream);
+/* The way back: disparity in the network's geometry -> disparity in the frame's geometry, in the frame's pixels, one launch.
+ * disp_px:  (batch,1,H,W) fp32, pixels of the network's geometry (what RT_DISP_PIXELS_F32 holds)
+ * mask_u8:  (batch,1,H,W) the 255 / 0 mask of rt_lr_consistency, or NULL
+ * out:      (batch,1,out_h,out_w) in out_kind: RT_DISP_PIXELS_F32 or RT_DISP_KITTI_U16
+ * out_mask_u8: (batch,1,out_h,out_w) uint8 or NULL;  valid_count: `batch` uint64 on the device or NULL, zeroed by the entry;
+ *           both only with mask_u8
+ * All fp32, nothing contracted.  Per axis (n source, m destination, index d), half-pixel centres (bilinear, align_corners = false):
+ *       sc = (float)n / (float)m;   p = ((float)d + 0.5f) * sc - 0.5f;   p = p < 0 ? 0 : p
+ *       i0 = min((int)floorf(p), n - 1);   i1 = min(i0 + 1, n - 1);   w1 = p - (float)i0;   w0 = 1.f - w1
+ *   top = D[y0][x0] * a0 + D[y0][x1] * a1,  bot likewise on y1,  v = (top * b0 + bot * b1) * r  with r = (float)out_w / (float)W
+ *   (disparities scale with the width ratio only).  RT_DISP_KITTI_U16: rintf(v * 256.f) saturated to [0, 65535] as rt_disparity_to_u16;
+ *   a NaN encodes to 0.
+ * With mask_u8: the nearest tap is x1 if a1 > 0.5f else x0, the same in y.  If all four taps are valid, v as above; otherwise
+ * v = D[nearest] * r (nothing is mixed with the zeros the check wrote).  The frame pixel is valid iff its nearest tap is; an invalid
+ * pixel is 0 in out and in out_mask_u8; a valid RT_DISP_KITTI_U16 value that encodes to 0 is raised to 1 (as rt_lr_consistency).
+ * out_h == H && out_w == W is legal: a copy / an encoding.  Factors within [1/6, 6] per axis, else RT_E_UNSUPPORTED; another kind, null
+ * disp_px / out, sizes < 1, out_mask_u8 / valid_count without mask_u8: error.  All found before anything is written. */
+int rt_disparity_to_frame(const void* disp_px, const void* mask_u8, int batch, int H, int W, void* out, int out_kind, int out_h,
+                          int out_w, void* out_mask_u8, void* valid_count, rtStream stream);
+
 /* ---- the viz node's debug panel (ros/packages/stereo_dnn_ros_viz/src/stereo_dnn_ros_viz_node.cpp) ---------------------------- */
 /* KITTI colour scheme of the viz node's dispToColor (:49-79): disp_px (n,1,H,W) fp32 pixels -> rgb8, rows dst_step >= 3W bytes apart,
  * images H * dst_step bytes apart; bytes between 3W and dst_step are not touched.  With the reference's fp32 tables

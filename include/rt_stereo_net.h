@@ -107,6 +107,39 @@ int rt_net_execute_frames_viz(rtStereoNet* net, const void* left_u8, const void*
                               int encoding, void* disp_px, void* viz_rgb8, int64_t viz_step, float max_disp, float max_diff_px,
                               void* mask_u8, void* valid_count, int batch, rtStream stream);
 
+/* Frames of any size in, disparity at the frame's size out, from one call; options travel in a struct that can grow.
+ * Launches: the front end (rt_preprocess_frames_u8 / _lr, or rt_preprocess_frames_u8_cv), the engine (one pass, batch or 2 * batch with
+ * a check), then
+ *   RT_GEOM_NET    as rt_net_execute_frames (copy / scale / 16-bit) or, with a check, rt_lr_consistency into the caller's buffers;
+ *   RT_GEOM_FRAME  the network's pixels (rt_disparity_scale by the model's scale, skipped where that is 1; with a check
+ *                  rt_lr_consistency in network geometry, in pixels, with its mask) into buffers the net owns, then
+ *                  rt_disparity_to_frame into the caller's (batch,1,src_h,src_w) buffers, which carries the mask over.
+ * The result is bit-identical to these op-level calls made by hand around rt_net_execute; with RT_RESIZE_AREA_DOWN and RT_GEOM_NET it
+ * is rt_net_execute_frames / rt_net_execute_frames_lr on the same arguments, refusals included.  The network-geometry disparity and mask
+ * are made on first use for max_batch, like the inputs.  Front and back end run outside the engine's graph, so frame and output
+ * pointers may rotate in graph mode.  stream == NULL: synchronous.  RT_GEOM_FRAME with RT_DISP_NET: RT_E_UNSUPPORTED.  A wrong
+ * struct_bytes, an unknown enum value, a NaN max_diff_px, mask_u8 / valid_count without a check, batch (2 * batch with a check) beyond
+ * max_batch, and whatever the op-level calls refuse: error before anything is written. */
+enum { RT_RESIZE_AREA_DOWN = 0 /* as rt_net_execute_frames: refuses up-scaling */, RT_RESIZE_CV_AREA = 1 /* rt_preprocess_frames_u8_cv */ };
+enum { RT_GEOM_NET = 0, RT_GEOM_FRAME = 1 };
+typedef struct rtFrameCall {
+    size_t struct_bytes;       /* sizeof(rtFrameCall): lets the struct grow */
+    const void* left_u8;       /* device frames as rt_net_execute_frames takes them */
+    const void* right_u8;
+    int src_h, src_w;
+    int64_t src_step;
+    int encoding;              /* RT_ENC_* */
+    int resize;                /* RT_RESIZE_* */
+    void* disp;
+    int disp_kind;             /* RT_DISP_* */
+    int geometry;              /* RT_GEOM_NET: (batch,1,net_h,net_w).  RT_GEOM_FRAME: (batch,1,src_h,src_w), the frame's pixels */
+    float max_diff_px;         /* < 0: no left-right check; >= 0: as rt_net_execute_frames_lr, 2 * batch <= max_batch */
+    void* mask_u8;             /* optional, only with a check; in the geometry of `disp` */
+    void* valid_count;
+    int batch;
+} rtFrameCall;
+int rt_net_execute_frames_ex(rtStereoNet* net, const rtFrameCall* call, rtStream stream);
+
 /* Per-launch timing through nvinfer1::IProfiler (single stream, one event pair per launch):
  * writes "name<TAB>milliseconds\n" lines into buf.  Returns 0 or an error. */
 int rt_net_profile(rtStereoNet* net, const void* left, const void* right, void* disp, int batch, char* buf,

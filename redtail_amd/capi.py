@@ -95,6 +95,9 @@ KERNEL_SYMBOLS = {
     "rt_preprocess_frames_u8_lr": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                            c_void_p]),
     "rt_lr_consistency": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rt_preprocess_frames_u8_cv": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                           c_void_p]),
+    "rt_disparity_to_frame": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "rt_disparity_to_color": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p]),
     "rt_viz_mosaic_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_int64, c_int,
                                  c_void_p]),
@@ -229,6 +232,20 @@ class KernelLib:
         2 KITTI uint16) with inconsistent pixels 0, uint8 mask (255 = consistent), right view's disparity, uint64 count per image"""
         self.check(self.lib.rt_lr_consistency(_ptr(net_disp), batch, h, w, scale, max_diff_px, _ptr(out), kind, _ptr(mask),
                                               _ptr(right_out), _ptr(valid_count), stream), "rt_lr_consistency")
+
+    def preprocess_frames_u8_cv(self, left, right, src_h, src_w, src_step, encoding, left_dst, right_dst, dst_h, dst_w, batch=1,
+                                mirror_twin=False, stream=None):
+        """preprocess_frames_u8 for any size: cv::resize(INTER_AREA) as a whole (box filter when neither axis grows, else two taps an axis);
+        mirror_twin: the destinations hold 2N images, [batch, 2N) the mirrored, swapped pair of preprocess_frames_u8_lr"""
+        self.check(self.lib.rt_preprocess_frames_u8_cv(_ptr(left), _ptr(right), src_h, src_w, src_step, encoding, _ptr(left_dst),
+                                                       _ptr(right_dst), dst_h, dst_w, batch, int(bool(mirror_twin)), stream),
+                   "rt_preprocess_frames_u8_cv")
+
+    def disparity_to_frame(self, disp_px, batch, h, w, out, out_h, out_w, kind=1, mask=None, out_mask=None, valid_count=None, stream=None):
+        """(N,1,h,w) fp32 disparity in the network's pixels (+ the uint8 mask of lr_consistency) -> (N,1,out_h,out_w) in the frame's
+        pixels, `kind` RT_DISP_PIXELS_F32 or RT_DISP_KITTI_U16; with a mask: the frame's uint8 mask and uint64 count per image"""
+        self.check(self.lib.rt_disparity_to_frame(_ptr(disp_px), _ptr(mask), batch, h, w, _ptr(out), kind, out_h, out_w, _ptr(out_mask),
+                                                  _ptr(valid_count), stream), "rt_disparity_to_frame")
 
     def corr_softargmax_pitched(self, l, r, out, batch, C, H, W, D, is_min, in_pitch, out_pitch, out_bstride=0,
                                 dtype=RT_F32, stream=None):
@@ -404,6 +421,8 @@ class ConvPlan:
 # ---------------------------------------------------------------------------------------------------
 RT_MODEL_RESNET18_2D, RT_MODEL_NVSMALL, RT_MODEL_NVTINY, RT_MODEL_RESNET18 = 0, 1, 2, 3
 RT_DISP_NET, RT_DISP_PIXELS_F32, RT_DISP_KITTI_U16 = 0, 1, 2          # rt_net_execute_frames: what `disp` receives
+RT_RESIZE_AREA_DOWN, RT_RESIZE_CV_AREA = 0, 1                         # rtFrameCall.resize
+RT_GEOM_NET, RT_GEOM_FRAME = 0, 1                                     # rtFrameCall.geometry
 MODEL_IDS = {"resnet18_2D": RT_MODEL_RESNET18_2D, "nvsmall": RT_MODEL_NVSMALL, "nvtiny": RT_MODEL_NVTINY,
              "resnet18": RT_MODEL_RESNET18}
 
@@ -419,6 +438,7 @@ NET_SYMBOLS = {
                                          c_void_p, c_float, c_int, c_void_p]),
     "rt_net_execute_frames_viz": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int64, c_float,
                                           c_float, c_void_p, c_void_p, c_int, c_void_p]),
+    "rt_net_execute_frames_ex": (c_int, [c_void_p, c_void_p, c_void_p]),
     "rt_net_profile": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_char_p, c_size_t]),
     "rt_net_num_layers": (c_int, [c_void_p]),
     "rt_net_num_launches": (c_int, [c_void_p]),
@@ -442,6 +462,13 @@ class NetOptions(ctypes.Structure):
     """rtNetOptions (include/rt_stereo_net.h)"""
     _fields_ = [("model", c_int), ("width", c_int), ("height", c_int), ("max_batch", c_int), ("weights_dtype", c_int), ("max_disp", c_int),
                 ("weights_path", c_char_p), ("blob", c_void_p), ("bytes", c_size_t), ("flags", ctypes.c_uint), ("comm", c_void_p), ("root", c_int)]
+
+
+class FrameCall(ctypes.Structure):
+    """rtFrameCall (include/rt_stereo_net.h)"""
+    _fields_ = [("struct_bytes", c_size_t), ("left_u8", c_void_p), ("right_u8", c_void_p), ("src_h", c_int), ("src_w", c_int),
+                ("src_step", c_int64), ("encoding", c_int), ("resize", c_int), ("disp", c_void_p), ("disp_kind", c_int), ("geometry", c_int),
+                ("max_diff_px", c_float), ("mask_u8", c_void_p), ("valid_count", c_void_p), ("batch", c_int)]
 
 
 def pack_weights(weights, fp16=False):
@@ -626,6 +653,17 @@ class StereoNet:
                                                                     _ptr(disp_px), _ptr(viz_rgb8), 6 * self.width if viz_step is None else viz_step,
                                                                     max_disp, max_diff_px, _ptr(mask), _ptr(valid_count), batch, stream),
                           "rt_net_execute_frames_viz")
+
+    def execute_frames_ex(self, left_u8, right_u8, encoding, disp, kind=RT_DISP_PIXELS_F32, geometry=RT_GEOM_FRAME, resize=RT_RESIZE_CV_AREA,
+                          max_diff_px=-1.0, mask=None, valid_count=None, batch=1, stream=None, src_step=None, src_w=None, struct_bytes=None):
+        """rt_net_execute_frames_ex: frames of any size in (resize = RT_RESIZE_CV_AREA; RT_RESIZE_AREA_DOWN refuses up-scaling as
+        execute_frames does), disparity out in the network's geometry (RT_GEOM_NET: (N,1,h,w)) or in the frame's (RT_GEOM_FRAME:
+        (N,1,src_h,src_w), the frame's pixels), with a left-right check when max_diff_px >= 0 (mask, valid_count in the geometry of disp;
+        2 * batch must fit max_batch).  Frames as for execute_frames."""
+        h, w, step = self._frame_geometry("rt_net_execute_frames_ex", left_u8, right_u8, encoding, batch, src_step, src_w)
+        call = FrameCall(ctypes.sizeof(FrameCall) if struct_bytes is None else struct_bytes, _ptr(left_u8), _ptr(right_u8), h, w, step, encoding,
+                         resize, _ptr(disp), kind, geometry, max_diff_px, _ptr(mask), _ptr(valid_count), batch)
+        self.netlib.check(self.netlib.lib.rt_net_execute_frames_ex(self.handle, ctypes.byref(call), stream), "rt_net_execute_frames_ex")
 
     def set_debug(self, on=True):
         """IExecutionContext::setDebugSync: synchronise every launch and range-check the input of every fp16-pipe convolution"""

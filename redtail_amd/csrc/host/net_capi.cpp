@@ -61,12 +61,16 @@ struct rtStereoNet {
     int model = RT_MODEL_RESNET18_2D;
     void* frame_in[2] = {nullptr, nullptr};       // rt_net_execute_frames: fp32 inputs and disparity for max_batch, made on first use
     void* frame_disp = nullptr;
+    void* frame_px = nullptr;                     // rt_net_execute_frames_ex, RT_GEOM_FRAME: network-geometry pixels and mask for max_batch
+    void* frame_mask = nullptr;
     ~rtStereoNet() {
         if (context) context->destroy();
         if (engine) engine->destroy();
         rt_free(frame_in[0]);
         rt_free(frame_in[1]);
         rt_free(frame_disp);
+        rt_free(frame_px);
+        rt_free(frame_mask);
     }
 };
 
@@ -379,6 +383,83 @@ extern "C" int rt_net_execute_frames_viz(rtStereoNet* net, const void* left_u8, 
                                viz_step, batch, stream);
     if (vrc == 0 && !stream) vrc = rt_stream_sync(nullptr);
     if (vrc != 0) return fail(std::string("rt_net_execute_frames_viz: ") + rt_last_error_string());
+    return 0;
+}
+
+// Frames of any size in, disparity in the frame's geometry out.  RT_RESIZE_AREA_DOWN with RT_GEOM_NET is the two entries above, called
+// as they are; everything else is the same sequence with rt_preprocess_frames_u8_cv in front and / or rt_disparity_to_frame behind.
+// Whatever an op-level call can refuse is refused by the front end, before anything is written: the back end's limits are the front
+// end's, and its other arguments are checked here.
+extern "C" int rt_net_execute_frames_ex(rtStereoNet* net, const rtFrameCall* c, rtStream stream) {
+    const std::string fn = "rt_net_execute_frames_ex: ";
+    if (!net || !net->context || !c) return fail(fn + "null pointer");
+    if (c->struct_bytes != sizeof(rtFrameCall))
+        return fail(fn + "struct_bytes " + std::to_string(c->struct_bytes) + " is not sizeof(rtFrameCall) = " + std::to_string(sizeof(rtFrameCall)));
+    if (!c->left_u8 || !c->right_u8 || !c->disp) return fail(fn + "null pointer");
+    if (c->resize != RT_RESIZE_AREA_DOWN && c->resize != RT_RESIZE_CV_AREA) return fail(fn + "unknown resize " + std::to_string(c->resize));
+    if (c->geometry != RT_GEOM_NET && c->geometry != RT_GEOM_FRAME) return fail(fn + "unknown geometry " + std::to_string(c->geometry));
+    if (c->disp_kind != RT_DISP_NET && c->disp_kind != RT_DISP_PIXELS_F32 && c->disp_kind != RT_DISP_KITTI_U16)
+        return fail(fn + "unknown disp_kind " + std::to_string(c->disp_kind));
+    if (c->encoding < RT_ENC_BGR8 || c->encoding > RT_ENC_RGBA8) return fail(fn + "unknown encoding " + std::to_string(c->encoding));
+    if (c->max_diff_px != c->max_diff_px) return fail(fn + "max_diff_px is not a number");
+    const bool check = c->max_diff_px >= 0.f;
+    if (!check && (c->mask_u8 || c->valid_count)) return fail(fn + "mask_u8 and valid_count need a check (max_diff_px >= 0)");
+    const int batch = c->batch, engine_batch = check ? 2 * batch : batch;
+    if (batch < 1 || (int64_t)(check ? 2 : 1) * batch > net->max_batch)
+        return fail(fn + "batch " + std::to_string(batch) + (check ? " with a check" : "") + " needs an engine batch of " +
+                    std::to_string((int64_t)(check ? 2 : 1) * batch) + ", max_batch is " + std::to_string(net->max_batch));
+    if (c->geometry == RT_GEOM_FRAME && c->disp_kind == RT_DISP_NET) {
+        fail(fn + "RT_GEOM_FRAME needs a disparity in pixels (RT_DISP_PIXELS_F32 / RT_DISP_KITTI_U16), not RT_DISP_NET");
+        return RT_E_UNSUPPORTED;
+    }
+    if (c->resize == RT_RESIZE_AREA_DOWN && c->geometry == RT_GEOM_NET)
+        return check ? rt_net_execute_frames_lr(net, c->left_u8, c->right_u8, c->src_h, c->src_w, c->src_step, c->encoding, c->disp, c->disp_kind,
+                                                c->mask_u8, nullptr, c->valid_count, c->max_diff_px, batch, stream)
+                     : rt_net_execute_frames(net, c->left_u8, c->right_u8, c->src_h, c->src_w, c->src_step, c->encoding, c->disp, c->disp_kind, batch,
+                                             stream);
+    const bool frame = c->geometry == RT_GEOM_FRAME;
+    const int H = net->height, W = net->width;
+    const int64_t pixels = (int64_t)H * W;
+    for (void** p : {&net->frame_in[0], &net->frame_in[1], &net->frame_disp}) {
+        const size_t bytes = (size_t)net->max_batch * pixels * (p == &net->frame_disp ? 1 : 3) * sizeof(float);
+        if (!*p && rt_malloc(p, bytes) != 0) return fail(fn + rt_last_error_string());
+    }
+    if (frame) {
+        if (!net->frame_px && rt_malloc(&net->frame_px, (size_t)net->max_batch * pixels * sizeof(float)) != 0) return fail(fn + rt_last_error_string());
+        if (!net->frame_mask && rt_malloc(&net->frame_mask, (size_t)net->max_batch * pixels) != 0) return fail(fn + rt_last_error_string());
+    }
+    int rc;
+    if (c->resize == RT_RESIZE_CV_AREA)
+        rc = rt_preprocess_frames_u8_cv(c->left_u8, c->right_u8, c->src_h, c->src_w, c->src_step, c->encoding, net->frame_in[0], net->frame_in[1], H,
+                                        W, batch, check ? 1 : 0, stream);
+    else
+        rc = (check ? rt_preprocess_frames_u8_lr : rt_preprocess_frames_u8)(c->left_u8, c->right_u8, c->src_h, c->src_w, c->src_step, c->encoding,
+                                                                            net->frame_in[0], net->frame_in[1], H, W, batch, stream);
+    if (rc != 0) return fail(fn + rt_last_error_string());
+    void* bindings[3] = {net->frame_in[0], net->frame_in[1], net->frame_disp};
+    const bool ok = stream ? net->context->enqueue(engine_batch, bindings, (cudaStream_t)stream, nullptr) : net->context->execute(engine_batch, bindings);
+    if (!ok) return fail(fn + net->log.last_error);
+    const float scale = net->model == RT_MODEL_RESNET18_2D ? (float)W : 1.f;            // as rt_net_execute_frames
+    const int64_t n = batch * pixels;
+    if (!frame) {
+        if (check) rc = rt_lr_consistency(net->frame_disp, batch, H, W, scale, c->max_diff_px, c->disp, c->disp_kind, c->mask_u8, nullptr, c->valid_count, stream);
+        else if (c->disp_kind == RT_DISP_NET) rc = rt_memcpy_d2d(c->disp, net->frame_disp, (size_t)n * sizeof(float), stream);
+        else if (c->disp_kind == RT_DISP_PIXELS_F32) rc = rt_disparity_scale(net->frame_disp, c->disp, n, scale, stream);
+        else rc = rt_disparity_to_u16(net->frame_disp, c->disp, n, 256.f * scale, stream);
+    } else if (check) {
+        rc = rt_lr_consistency(net->frame_disp, batch, H, W, scale, c->max_diff_px, net->frame_px, RT_DISP_PIXELS_F32, net->frame_mask, nullptr, nullptr, stream);
+        if (rc == 0)
+            rc = rt_disparity_to_frame(net->frame_px, net->frame_mask, batch, H, W, c->disp, c->disp_kind, c->src_h, c->src_w, c->mask_u8, c->valid_count, stream);
+    } else {
+        const void* px = net->frame_disp;              // the 3-D models' output is in pixels already
+        if (net->model == RT_MODEL_RESNET18_2D) {
+            rc = rt_disparity_scale(net->frame_disp, net->frame_px, n, scale, stream);
+            px = net->frame_px;
+        }
+        if (rc == 0) rc = rt_disparity_to_frame(px, nullptr, batch, H, W, c->disp, c->disp_kind, c->src_h, c->src_w, nullptr, nullptr, stream);
+    }
+    if (rc == 0 && !stream) rc = rt_stream_sync(nullptr);
+    if (rc != 0) return fail(fn + rt_last_error_string());
     return 0;
 }
 

@@ -217,6 +217,102 @@ preprocess_frames_lr_kernel(const unsigned char* __restrict__ left, const unsign
     }
 }
 
+// cv::resize(INTER_AREA) when either axis grows (reference stereo_dnn_ros_node.cpp:42-58 calls it for whatever the camera sends).
+// OpenCV has true area interpolation for shrinking both ways only; otherwise BOTH axes -- the shrinking one included -- take the two-tap
+// set-up of its area_mode branch.  Per axis, source size n, destination size m, destination index d, positions in double, weight fp32:
+//   inv = (double)m / n,  scale = 1.0 / inv,  s = (int)floor(d * scale),  f = (float)((d + 1) - (s + 1) * inv),
+//   f = f <= 0 ? 0 : f - floorf(f),  s >= n - 1: s = n - 1, f = 0;   taps: s with weight 1.f - f, min(s + 1, n - 1) with weight f
+// (s + 1) * inv is rounded before the subtraction (no FMA): where d * scale lands on an integer the weight depends on it.
+__device__ static __forceinline__ void cv_area_tap(int d, int n, int m, int& s0, int& s1, float& w1) {
+#pragma clang fp contract(off)
+    const double inv = (double)m / (double)n, scale = 1.0 / inv;
+    int s = (int)floor((double)d * scale);
+    const double t = (double)(s + 1) * inv;
+    float f = (float)((double)(d + 1) - t);
+    f = f <= 0.f ? 0.f : f - floorf(f);
+    if (s >= n - 1) { s = n - 1; f = 0.f; }
+    s0 = s;
+    s1 = s + 1 < n ? s + 1 : n - 1;
+    w1 = f;
+}
+
+template <int BPP, bool DWORD>
+__device__ static __forceinline__ void frame_pixel(const unsigned char* px, unsigned& c0, unsigned& c1, unsigned& c2) {
+    if constexpr (DWORD) {
+        const unsigned v = *reinterpret_cast<const unsigned*>(px);
+        c0 = v & 0xffu; c1 = (v >> 8) & 0xffu; c2 = (v >> 16) & 0xffu;
+    } else {
+        c0 = px[0]; c1 = px[1]; c2 = px[2];
+    }
+}
+
+// The pair batch of preprocess_frames_kernel (TWIN: plus the mirrored, swapped twin of preprocess_frames_lr_kernel, same exchange across
+// the wave) through the two-tap filter above.  Same block shape: 64 destination columns x 4 rows, the x taps of the columns and the y taps
+// of the rows built once into LDS (double-precision work) by wave 0 and by lanes 0-3 of wave 1.  A pixel has four source pixels, all
+// loaded before the first is used.  Per channel, fp32, x first, every product and sum rounded on its own (contraction is off):
+//   row_j = S[y_j][x0] * a0 + S[y_j][x1] * a1,   v = row_0 * b0 + row_1 * b1,   then colour order, / 255, planes as preprocess_frames_kernel
+// grid = (ceil(dw/64), ceil(dh/4), 2 * batch): z < batch -> left frame z, else right frame z - batch
+template <int BPP, bool DWORD, bool TWIN>
+__global__ void __launch_bounds__(256)
+preprocess_frames_cv_kernel(const unsigned char* __restrict__ left, const unsigned char* __restrict__ right, int sh, int sw, int64_t step,
+                            bool rgb_order, float* __restrict__ dleft, float* __restrict__ dright, int dh, int dw, int batch) {
+#pragma clang fp contract(off)
+    __shared__ int s_x0[kFramesCols], s_x1[kFramesCols], s_y0[kFramesRows], s_y1[kFramesRows];
+    __shared__ float s_a1[kFramesCols], s_b1[kFramesRows];
+    const int tx = threadIdx.x % kFramesCols, ty = threadIdx.x / kFramesCols;
+    const int dx = blockIdx.x * kFramesCols + tx, dy = blockIdx.y * kFramesRows + ty;
+    const bool second = (int)blockIdx.z >= batch;
+    const int n = second ? blockIdx.z - batch : blockIdx.z;
+    const unsigned char* s = (second ? right : left) + (int64_t)n * sh * step;
+    const int64_t plane = (int64_t)dh * dw;
+    float* d = (second ? dright : dleft) + (int64_t)n * 3 * plane;
+    if (ty == 0 && dx < dw) {
+        cv_area_tap(dx, sw, dw, s_x0[tx], s_x1[tx], s_a1[tx]);
+    } else if (ty == 1 && tx < kFramesRows && (int)blockIdx.y * kFramesRows + tx < dh) {
+        cv_area_tap(blockIdx.y * kFramesRows + tx, sh, dh, s_y0[tx], s_y1[tx], s_b1[tx]);
+    }
+    __syncthreads();
+    if (dy >= dh) return;                              // a whole wave: ty is the wave index
+    float v0 = 0.f, v1 = 0.f, v2 = 0.f;               // channels in memory order: B,G,R or R,G,B
+    if (dx < dw) {
+        const float a1 = s_a1[tx], a0 = 1.f - a1, b1 = s_b1[ty], b0 = 1.f - b1;
+        const unsigned char* r0 = s + (int64_t)s_y0[ty] * step;
+        const unsigned char* r1 = s + (int64_t)s_y1[ty] * step;
+        const int64_t o0 = (int64_t)s_x0[tx] * BPP, o1 = (int64_t)s_x1[tx] * BPP;
+        unsigned p[4][3];
+        frame_pixel<BPP, DWORD>(r0 + o0, p[0][0], p[0][1], p[0][2]);
+        frame_pixel<BPP, DWORD>(r0 + o1, p[1][0], p[1][1], p[1][2]);
+        frame_pixel<BPP, DWORD>(r1 + o0, p[2][0], p[2][1], p[2][2]);
+        frame_pixel<BPP, DWORD>(r1 + o1, p[3][0], p[3][1], p[3][2]);
+        float v[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float top = (float)p[0][c] * a0 + (float)p[1][c] * a1;
+            const float bot = (float)p[2][c] * a0 + (float)p[3][c] * a1;
+            v[c] = top * b0 + bot * b1;
+        }
+        v0 = v[0]; v1 = v[1]; v2 = v[2];
+    }
+    const float r = (rgb_order ? v0 : v2) / 255.f, g = v1 / 255.f, b = (rgb_order ? v2 : v0) / 255.f;
+    const int64_t o = (int64_t)dy * dw + dx;
+    if (dx < dw) {
+        d[o] = r;                     // RGB planes
+        d[plane + o] = g;
+        d[2 * plane + o] = b;
+    }
+    if constexpr (TWIN) {              // as preprocess_frames_lr_kernel: lanes past the row's end stay in the wave for the exchange
+        float* m = (second ? dleft : dright) + (int64_t)(batch + n) * 3 * plane;
+        const float mr = __shfl(r, kFramesCols - 1 - tx), mg = __shfl(g, kFramesCols - 1 - tx), mb = __shfl(b, kFramesCols - 1 - tx);
+        const int mx = dw - kFramesCols - (int)blockIdx.x * kFramesCols + tx;
+        if (mx >= 0) {
+            const int64_t mo = (int64_t)dy * dw + mx;
+            m[mo] = mr;
+            m[plane + mo] = mg;
+            m[2 * plane + mo] = mb;
+        }
+    }
+}
+
 // Left-right consistency check, mask and output encoding of a (2 * batch, 1, H, W) engine output whose images [batch, 2 batch) are the
 // mirrored right views (preprocess_frames_lr_kernel).  All in fp32, every operation rounded on its own (contraction is off in this body):
 //   dL(x) = L[y][x] * scale,  dR(x) = R[y][W-1-x] * scale,  xr = rintf((float)x - dL(x)),
@@ -327,6 +423,125 @@ lr_consistency_kernel(const float* __restrict__ net, int batch, int H, int W, fl
 #pragma unroll
         for (int k = 0; k < 4; k++) c += __builtin_popcountll(__ballot(ok[k]));
         if ((threadIdx.x & 63) == 0 && c) atomicAdd(count + n, (unsigned long long)c);
+    }
+}
+
+// Disparity of the network's geometry (H x W, pixels) -> the frame's geometry (oh x ow, the frame's pixels): bilinear with half-pixel
+// centres (interpolate(mode="bilinear", align_corners=False)) times r = (float)ow / (float)W.  All fp32, contraction off.  Per axis
+// (n source, m destination, index d):
+//   sc = (float)n / (float)m,  p = max(((float)d + 0.5f) * sc - 0.5f, 0),  i0 = min((int)floorf(p), n - 1),  i1 = min(i0 + 1, n - 1),
+//   w1 = p - (float)i0,  w0 = 1.f - w1
+//   v = ((D[y0][x0] * a0 + D[y0][x1] * a1) * b0 + (D[y1][x0] * a0 + D[y1][x1] * a1) * b1) * r
+// MASKED (the 255 / 0 mask of lr_consistency_kernel, network geometry): the nearest tap is x1 if a1 > 0.5f else x0, same in y; with all
+// four taps valid v as above, otherwise v = D[nearest] * r (nothing is mixed with the zeros the check wrote); the frame pixel is valid iff
+// its nearest tap is, an invalid one is 0 in out and in the mask; a valid 16-bit value that encodes to 0 is raised to 1.
+// U16: rintf(v * 256.f) saturated to [0, 65535], NaN -> 0.
+// Output addressing as lr_consistency_kernel: a lane owns 4 consecutive pixels of one image's oh * ow plane as a flat run, groups laid on
+// 16-byte boundaries of the fp32 output (`vec`), head and tail groups element by element; row and column are carried per element.  The
+// 16 gathers of a lane stay within two source rows per output row and are all issued before the first use.
+// count (zeroed by the host entry): a ballot per element slot, the four waves' sums through LDS, one atomic per block -- one per wave,
+// 1800 adds to one address for a 1242 x 375 frame, took the launch from 5.6 to 27.5 us.
+// grid = (ceil(G / 256), batch) with G = (oh*ow + 6) / 4 groups
+__device__ static __forceinline__ void frame_tap(int d, float sc, int n, int& i0, int& i1, float& w1) {
+#pragma clang fp contract(off)
+    float p = ((float)d + 0.5f) * sc - 0.5f;
+    p = p < 0.f ? 0.f : p;
+    const int i = (int)floorf(p);
+    i0 = i < n - 1 ? i : n - 1;
+    i1 = i0 + 1 < n - 1 ? i0 + 1 : n - 1;
+    w1 = p - (float)i0;
+}
+
+template <bool U16, bool MASKED>
+__global__ void __launch_bounds__(256)
+disparity_to_frame_kernel(const float* __restrict__ disp, const unsigned char* __restrict__ mask, int H, int W, void* __restrict__ out_v,
+                          int oh, int ow, unsigned char* __restrict__ omask, unsigned long long* __restrict__ count, int vec) {
+#pragma clang fp contract(off)
+    using T = typename LrOut<U16 ? 2 : 1>::type;
+    const int n = blockIdx.y;
+    const int64_t plane = (int64_t)oh * ow;
+    const int64_t obase = (int64_t)n * plane;
+    const float* D = disp + (int64_t)n * H * W;
+    const unsigned char* M = MASKED ? mask + (int64_t)n * H * W : nullptr;
+    T* out = static_cast<T*>(out_v) + obase;
+    if (omask) omask += obase;
+    const float sx = (float)W / (float)ow, sy = (float)H / (float)oh, r = (float)ow / (float)W;
+    const int a = vec ? (int)(obase & 3) : 0;
+    const int64_t e0 = 4 * ((int64_t)blockIdx.x * 256 + threadIdx.x) - a;      // first element of the group, image-local (< 0 in the head group)
+    const int lo = e0 < 0 ? (int)-e0 : 0;
+    const int hi = e0 + 4 <= plane ? 4 : (int)(plane - e0);                    // <= 0: no element (lanes past the plane still vote below)
+    const bool full = vec && lo == 0 && hi == 4;
+    int y = 0, x = 0;
+    if (lo < hi) {
+        y = (int)((e0 + lo) / ow);
+        x = (int)((e0 + lo) - (int64_t)y * ow);
+    }
+    float t[4][4], a1[4], b1[4];
+    unsigned m[4][4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {                      // taps and loads of all four pixels first (clamped to pixel 0 for a slot without one)
+        const bool in = k >= lo && k < hi;
+        int x0, x1, y0, y1;
+        frame_tap(in ? x : 0, sx, W, x0, x1, a1[k]);
+        frame_tap(in ? y : 0, sy, H, y0, y1, b1[k]);
+        const int64_t r0 = (int64_t)y0 * W, r1 = (int64_t)y1 * W;
+        t[k][0] = D[r0 + x0]; t[k][1] = D[r0 + x1]; t[k][2] = D[r1 + x0]; t[k][3] = D[r1 + x1];
+        if constexpr (MASKED) {
+            m[k][0] = M[r0 + x0]; m[k][1] = M[r0 + x1]; m[k][2] = M[r1 + x0]; m[k][3] = M[r1 + x1];
+        }
+        if (in && ++x == ow) { x = 0; y++; }
+    }
+    T ov[4];
+    unsigned ok[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const bool in = k >= lo && k < hi;
+        const float a0 = 1.f - a1[k], b0 = 1.f - b1[k];
+        const float top = t[k][0] * a0 + t[k][1] * a1[k];
+        const float bot = t[k][2] * a0 + t[k][3] * a1[k];
+        float v = (top * b0 + bot * b1[k]) * r;
+        bool valid = in;
+        if constexpr (MASKED) {
+            const int nt = (b1[k] > 0.5f ? 2 : 0) + (a1[k] > 0.5f ? 1 : 0);
+            const unsigned mn = nt == 0 ? m[k][0] : (nt == 1 ? m[k][1] : (nt == 2 ? m[k][2] : m[k][3]));
+            const float tn = nt == 0 ? t[k][0] : (nt == 1 ? t[k][1] : (nt == 2 ? t[k][2] : t[k][3]));
+            if (!(m[k][0] && m[k][1] && m[k][2] && m[k][3])) v = tn * r;
+            valid = in && mn != 0;
+        }
+        T o;
+        if constexpr (U16) {
+            const float q = rintf(v * 256.f);
+            o = (T)(q > 0.f ? (q < 65535.f ? q : 65535.f) : 0.f);              // NaN -> 0
+            if (MASKED && o == 0) o = (T)1;
+        } else {
+            o = v;
+        }
+        ov[k] = valid ? o : (T)0;
+        ok[k] = valid ? 1u : 0u;
+    }
+    if (full) {
+        if constexpr (U16) *reinterpret_cast<uint2*>(out + e0) = make_uint2((unsigned)ov[0] | ((unsigned)ov[1] << 16), (unsigned)ov[2] | ((unsigned)ov[3] << 16));
+        else *reinterpret_cast<float4*>(out + e0) = make_float4(ov[0], ov[1], ov[2], ov[3]);
+        if (MASKED && omask) *reinterpret_cast<unsigned*>(omask + e0) = (ok[0] | (ok[1] << 8) | (ok[2] << 16) | (ok[3] << 24)) * 255u;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (k < lo || k >= hi) continue;
+            out[e0 + k] = ov[k];
+            if (MASKED && omask) omask[e0 + k] = (unsigned char)(ok[k] * 255u);
+        }
+    }
+    if (MASKED && count) {                             // (uniform: every lane of every wave is still here)
+        __shared__ int s_count[4];
+        int c = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) c += __builtin_popcountll(__ballot(ok[k]));
+        if ((threadIdx.x & 63) == 0) s_count[threadIdx.x >> 6] = c;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            c = s_count[0] + s_count[1] + s_count[2] + s_count[3];
+            if (c) atomicAdd(count + n, (unsigned long long)c);
+        }
     }
 }
 

@@ -677,6 +677,73 @@ extern "C" int rt_preprocess_frames_u8_lr(const void* left, const void* right, i
                              dst_w, batch, s);
 }
 
+// The whole of cv::resize(INTER_AREA) as the node calls it: the box filter above when neither axis grows (the same code: bit-identical),
+// otherwise the two-tap form on both axes (preprocess_frames_cv_kernel); mirror_twin: plus the twin of rt_preprocess_frames_u8_lr
+extern "C" int rt_preprocess_frames_u8_cv(const void* left, const void* right, int src_h, int src_w, int64_t src_step, int encoding,
+                                          void* left_dst, void* right_dst, int dst_h, int dst_w, int batch, int mirror_twin, rtStream s) {
+    const char* fn = "rt_preprocess_frames_u8_cv";
+    RT_REQUIRE(left && right && left_dst && right_dst, "%s: null pointer", fn);
+    RT_REQUIRE(encoding >= RT_ENC_BGR8 && encoding <= RT_ENC_RGBA8, "%s: unknown encoding %d", fn, encoding);
+    RT_REQUIRE(src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0 && batch > 0 && batch <= 32767 && dst_h <= 4 * 65535, "%s: bad dims", fn);
+    if (dst_h <= src_h && dst_w <= src_w)
+        return preprocess_frames(fn, mirror_twin != 0, left, right, src_h, src_w, src_step, encoding, left_dst, right_dst, dst_h, dst_w, batch, s);
+    const int bpp = encoding == RT_ENC_BGRA8 || encoding == RT_ENC_RGBA8 ? 4 : 3;
+    RT_REQUIRE(src_step >= (int64_t)src_w * bpp, "%s: row step %lld is shorter than %d pixels of %d bytes", fn, (long long)src_step, src_w,
+               bpp);
+    if ((float)src_w / dst_w > 6.f || (float)src_h / dst_h > 6.f || (float)dst_w / src_w > 6.f || (float)dst_h / src_h > 6.f)
+        return fail(RT_E_UNSUPPORTED, "%s: scale factors outside [1/6, 6] (%dx%d -> %dx%d) are not implemented", fn, src_w, src_h, dst_w, dst_h);
+    const bool rgb = encoding == RT_ENC_RGB8 || encoding == RT_ENC_RGBA8;
+    const bool aligned = bpp == 4 && ((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right) | (uintptr_t)src_step) & 3) == 0;
+    const dim3 grid((unsigned)rt::cdiv(dst_w, rt::kFramesCols), (unsigned)rt::cdiv(dst_h, rt::kFramesRows), (unsigned)(2 * batch));
+    const dim3 block(rt::kFramesCols * rt::kFramesRows);
+    const unsigned char *l8 = static_cast<const unsigned char*>(left), *r8 = static_cast<const unsigned char*>(right);
+    float *lf = static_cast<float*>(left_dst), *rf = static_cast<float*>(right_dst);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, S(s), l8, r8, src_h, src_w, src_step, rgb, lf, rf, dst_h, dst_w, batch);
+    };
+    if (mirror_twin) {
+        if (bpp == 3) launch(rt::preprocess_frames_cv_kernel<3, false, true>);
+        else if (aligned) launch(rt::preprocess_frames_cv_kernel<4, true, true>);
+        else launch(rt::preprocess_frames_cv_kernel<4, false, true>);
+    } else {
+        if (bpp == 3) launch(rt::preprocess_frames_cv_kernel<3, false, false>);
+        else if (aligned) launch(rt::preprocess_frames_cv_kernel<4, true, false>);
+        else launch(rt::preprocess_frames_cv_kernel<4, false, false>);
+    }
+    RT_LAUNCH_CHECK("preprocess_frames_cv_kernel");
+    return 0;
+}
+
+// network-geometry disparity in pixels (+ the mask of rt_lr_consistency) -> the frame's geometry and pixels (disparity_to_frame_kernel)
+extern "C" int rt_disparity_to_frame(const void* disp_px, const void* mask_u8, int batch, int H, int W, void* out, int out_kind, int out_h,
+                                     int out_w, void* out_mask_u8, void* valid_count, rtStream s) {
+    RT_REQUIRE(disp_px && out, "rt_disparity_to_frame: null pointer");
+    RT_REQUIRE(batch >= 1 && batch <= 32767 && H >= 1 && W >= 1 && out_h >= 1 && out_w >= 1 && (int64_t)H * W < ((int64_t)1 << 31) &&
+               (int64_t)out_h * out_w < ((int64_t)1 << 31), "rt_disparity_to_frame: bad dims");
+    RT_REQUIRE(out_kind == RT_DISP_PIXELS_F32 || out_kind == RT_DISP_KITTI_U16, "rt_disparity_to_frame: unknown out_kind %d", out_kind);
+    RT_REQUIRE(mask_u8 || (!out_mask_u8 && !valid_count), "rt_disparity_to_frame: out_mask_u8 and valid_count need mask_u8");
+    if ((float)W / out_w > 6.f || (float)H / out_h > 6.f || (float)out_w / W > 6.f || (float)out_h / H > 6.f)
+        return fail(RT_E_UNSUPPORTED, "rt_disparity_to_frame: scale factors outside [1/6, 6] (%dx%d -> %dx%d) are not implemented", W, H, out_w, out_h);
+    if (valid_count) RT_HIP(hipMemsetAsync(valid_count, 0, (size_t)batch * sizeof(unsigned long long), S(s)));
+    // 16-byte (fp32) / 8-byte (16-bit) stores need the output 16-byte aligned, the mask's 4-byte stores the mask 4-byte aligned
+    const int vec = aligned16(out) && (reinterpret_cast<uintptr_t>(out_mask_u8) & 3) == 0;
+    const int64_t groups = ((int64_t)out_h * out_w + 3 + 3) / 4;             // + 3: the head group of an image that starts off a 16-byte boundary
+    const dim3 grid((unsigned)rt::cdiv(groups, 256), (unsigned)batch);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, S(s), static_cast<const float*>(disp_px), static_cast<const unsigned char*>(mask_u8), H, W,
+                           out, out_h, out_w, static_cast<unsigned char*>(out_mask_u8), static_cast<unsigned long long*>(valid_count), vec);
+    };
+    if (out_kind == RT_DISP_KITTI_U16) {
+        if (mask_u8) launch(rt::disparity_to_frame_kernel<true, true>);
+        else launch(rt::disparity_to_frame_kernel<true, false>);
+    } else {
+        if (mask_u8) launch(rt::disparity_to_frame_kernel<false, true>);
+        else launch(rt::disparity_to_frame_kernel<false, false>);
+    }
+    RT_LAUNCH_CHECK("disparity_to_frame_kernel");
+    return 0;
+}
+
 // left-right consistency check + mask + output encoding of a (2 batch, 1, H, W) engine output (lr_consistency_kernel)
 extern "C" int rt_lr_consistency(const void* net_disp, int batch, int H, int W, float scale, float max_diff_px, void* out, int out_kind,
                                  void* mask_u8, void* right_out, void* valid_count, rtStream s) {
