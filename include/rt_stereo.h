@@ -264,6 +264,44 @@ int rt_preprocess_frames_u8_cv(const void* left_u8, const void* right_u8, int sr
 int rt_disparity_to_frame(const void* disp_px, const void* mask_u8, int batch, int H, int W, void* out, int out_kind, int out_h,
                           int out_w, void* out_mask_u8, void* valid_count, rtStream stream);
 
+/* ---- depth and a point cloud out (no counterpart in the reference; what stereo_image_proc publishes behind such a node) --------- */
+/* A rectified pair in the geometry of the OUTPUT (out_h x out_w), from sensor_msgs/CameraInfo: P of the left camera gives
+ * fx = P[0], fy = P[5], cx = P[2], cy = P[6] (cx, cy in pixel-index units: pixel u has its centre at u); P of the right camera gives
+ * baseline = -P_right[3] / P_right[0] in metres (> 0) and doffs = P_right[2] - P_left[2] in pixels (0 for a ZED or a
+ * stereoRectify with CALIB_ZERO_DISPARITY). */
+typedef struct rtStereoCamera {
+    float fx, fy, cx, cy;
+    float baseline;
+    float doffs;
+} rtStereoCamera;
+/* REP 118 depth images: 32FC1 metres, NaN (0x7fc00000) = no value; 16UC1 millimetres, 0 = no value */
+enum { RT_DEPTH_M_F32 = 0, RT_DEPTH_MM_U16 = 1 };
+/* rt_disparity_to_frame followed, without a trip through memory, by the reprojection.  disp_px, mask_u8, H, W, out_h, out_w, disp_out /
+ * disp_kind, out_mask_u8 and valid_count are rt_disparity_to_frame's arguments (disp_out its `out`): those three outputs are bit-identical
+ * to what it writes and follow its validity `valid0` (true without a mask), not the depth range.  Every output may be NULL, one at
+ * least must be given.  All fp32, nothing contracted, IEEE divisions.  For output pixel (row r, column u) with resampled disparity v:
+ *   den = v + doffs;  ok = valid0 && den > 0 && den finite;  Z = fB / den  with fB = fx * baseline (formed once, in fp32);
+ *   ok = ok && Z >= min_depth && Z <= max_depth;   X = (((float)u - cx) / fx) * Z;   Y = (((float)r - cy) / fy) * Z
+ *   depth          (batch,1,out_h,out_w): RT_DEPTH_M_F32  ok ? Z : NaN;   RT_DEPTH_MM_U16  ok ? max(1, sat_u16(rintf(Z * 1000.f))) : 0
+ *   points         (batch,out_h,out_w) records of 16 bytes {float x, y, z; uint32 rgb = R << 16 | G << 8 | B} (PCL's PointXYZRGB packing:
+ *                  PointCloud2 fields x / y / z / rgb at offsets 0 / 4 / 8 / 12, point_step 16); x = y = z = NaN where not ok, the colour
+ *                  is written for every pixel (is_dense = false)
+ *   points_compact the ok records of image n in row-major order from byte n * out_h * out_w * 16 on (bytes behind the last one are not
+ *                  touched), and count[n] (`batch` uint64 on the device) their number; count alone is legal.  The order is deterministic.
+ *   colour         the left frames, out_h x out_w pixels in `encoding` (RT_ENC_*), rows color_step bytes apart, addressed as
+ *                  rt_preprocess_frames_u8 addresses frames; alpha is dropped; color_u8 == NULL: rgb = 0
+ * A compact cloud or a count needs `workspace`, device memory of rt_points_workspace_bytes(batch, out_h, out_w) bytes, and one more
+ * launch than the single one everything else takes.  A cloud must start on a 16-byte boundary.
+ * Errors, found before anything is written: null disp_px or cam; no output; sizes < 1; fx, fy or baseline not finite or not > 0; cx, cy
+ * or doffs not finite; min_depth NaN or < 0; max_depth NaN or < min_depth (+inf is legal); an unknown kind of a given output; with a
+ * colour an unknown encoding or a color_step shorter than a row; points_compact without count; out_mask_u8 / valid_count without mask_u8;
+ * a missing or short workspace; a cloud off a 16-byte boundary.  Factors outside [1/6, 6] per axis: RT_E_UNSUPPORTED. */
+size_t rt_points_workspace_bytes(int batch, int out_h, int out_w);
+int rt_disparity_to_points(const void* disp_px, const void* mask_u8, int batch, int H, int W, int out_h, int out_w,
+                           const rtStereoCamera* cam, float min_depth, float max_depth, const void* color_u8, int64_t color_step,
+                           int encoding, void* disp_out, int disp_kind, void* out_mask_u8, void* valid_count, void* depth, int depth_kind,
+                           void* points, void* points_compact, void* count, void* workspace, size_t workspace_bytes, rtStream stream);
+
 /* ---- the viz node's debug panel (ros/packages/stereo_dnn_ros_viz/src/stereo_dnn_ros_viz_node.cpp) ---------------------------- */
 /* KITTI colour scheme of the viz node's dispToColor (:49-79): disp_px (n,1,H,W) fp32 pixels -> rgb8, rows dst_step >= 3W bytes apart,
  * images H * dst_step bytes apart; bytes between 3W and dst_step are not touched.  With the reference's fp32 tables

@@ -140,6 +140,31 @@ typedef struct rtFrameCall {
 } rtFrameCall;
 int rt_net_execute_frames_ex(rtStereoNet* net, const rtFrameCall* call, rtStream stream);
 
+/* rt_net_execute_frames_ex in frame geometry with a depth image and / or a point cloud beside (or instead of) the disparity: the same
+ * sequence -- front end, one engine pass (2 * batch with a check), rt_disparity_scale or rt_lr_consistency into the net-owned
+ * network-geometry buffers -- with rt_disparity_to_points (rt_stereo.h, where depth, cloud and their validity are defined) in the place of
+ * rt_disparity_to_frame.  The result is bit-identical to those op-level calls made by hand around rt_net_execute.
+ *   call   as rt_net_execute_frames_ex takes it.  call->geometry must be RT_GEOM_FRAME: depth and cloud exist in the camera's own geometry
+ *          only, so the caller never rescales intrinsics; RT_GEOM_NET: RT_E_UNSUPPORTED.  call->disp may be NULL if `out` requests
+ *          something; otherwise disp_kind, mask_u8 and valid_count (the check's validity, carried over) are RT_GEOM_FRAME's.
+ *   out    camera: the CAMERA's calibration in the frame's geometry (src_h x src_w), used as it is; depth (batch,1,src_h,src_w) in
+ *          depth_kind, points (organised cloud), points_compact + count (valid points only; count = points that pass the check AND
+ *          the depth range), each or NULL.  The colour of a cloud is call->left_u8 itself.  out == NULL: rt_net_execute_frames_ex.
+ * The workspace of a compact cloud is a buffer the net owns, made on first use for max_batch.  The op runs outside the engine's graph, so
+ * every pointer may rotate in graph mode; stream == NULL: synchronous.  Whatever rt_net_execute_frames_ex or rt_disparity_to_points
+ * refuse, and a wrong struct_bytes of either struct: error before anything is written. */
+typedef struct rtDepthCall {
+    size_t struct_bytes;       /* sizeof(rtDepthCall) */
+    rtStereoCamera camera;
+    float min_depth, max_depth;
+    void* depth;
+    int depth_kind;            /* RT_DEPTH_* */
+    void* points;
+    void* points_compact;
+    void* count;
+} rtDepthCall;
+int rt_net_execute_frames_3d(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out, rtStream stream);
+
 /* Per-launch timing through nvinfer1::IProfiler (single stream, one event pair per launch):
  * writes "name<TAB>milliseconds\n" lines into buf.  Returns 0 or an error. */
 int rt_net_profile(rtStereoNet* net, const void* left, const void* right, void* disp, int batch, char* buf,

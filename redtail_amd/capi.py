@@ -21,6 +21,8 @@ RT_ACT_NONE, RT_ACT_ELU, RT_ACT_SIGMOID = 0, 1, 2
 
 RT_ENC_BGR8, RT_ENC_RGB8, RT_ENC_BGRA8, RT_ENC_RGBA8 = 0, 1, 2, 3     # sensor_msgs/Image encodings (rt_preprocess_frames_u8)
 ENC_BYTES = {RT_ENC_BGR8: 3, RT_ENC_RGB8: 3, RT_ENC_BGRA8: 4, RT_ENC_RGBA8: 4}
+RT_DISP_NET, RT_DISP_PIXELS_F32, RT_DISP_KITTI_U16 = 0, 1, 2          # forms of a disparity output (rt_lr_consistency, rt_net_execute_frames)
+RT_DEPTH_M_F32, RT_DEPTH_MM_U16 = 0, 1                                # REP 118 depth images (rt_disparity_to_points)
 RT_HINT_THROUGHPUT = 1     # include/rt_stereo.h
 RT_CONV_EXACT_FP32 = 1     # rtConv2dDesc.flags / rtConv3dDesc.flags / rtNetOptions.flags
 
@@ -32,6 +34,12 @@ class RtError(RuntimeError):
 class Conv2dDesc(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("Cin", "Cout", "Hin", "Win", "KH", "KW", "stride", "pad_h", "pad_w", "act",
                                      "has_residual", "dtype", "flags")]
+
+
+class StereoCamera(ctypes.Structure):
+    """rtStereoCamera (include/rt_stereo.h): a rectified pair in the geometry of the output; from sensor_msgs/CameraInfo fx = P[0], fy = P[5],
+    cx = P[2], cy = P[6] of the left camera, baseline = -P_right[3] / P_right[0] (metres), doffs = P_right[2] - P_left[2] (pixels)"""
+    _fields_ = [(n, c_float) for n in ("fx", "fy", "cx", "cy", "baseline", "doffs")]
 
 
 class Conv3dDesc(ctypes.Structure):
@@ -98,6 +106,10 @@ KERNEL_SYMBOLS = {
     "rt_preprocess_frames_u8_cv": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                            c_void_p]),
     "rt_disparity_to_frame": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "rt_points_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "rt_disparity_to_points": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(StereoCamera), c_float, c_float, c_void_p,
+                                       c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_size_t, c_void_p]),
     "rt_disparity_to_color": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p]),
     "rt_viz_mosaic_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_int64, c_int,
                                  c_void_p]),
@@ -246,6 +258,28 @@ class KernelLib:
         pixels, `kind` RT_DISP_PIXELS_F32 or RT_DISP_KITTI_U16; with a mask: the frame's uint8 mask and uint64 count per image"""
         self.check(self.lib.rt_disparity_to_frame(_ptr(disp_px), _ptr(mask), batch, h, w, _ptr(out), kind, out_h, out_w, _ptr(out_mask),
                                                   _ptr(valid_count), stream), "rt_disparity_to_frame")
+
+    def points_workspace_bytes(self, batch, out_h, out_w):
+        """bytes of device workspace disparity_to_points needs for a compact cloud or a count"""
+        return self.lib.rt_points_workspace_bytes(batch, out_h, out_w)
+
+    def disparity_to_points(self, disp_px, batch, h, w, out_h, out_w, camera, min_depth=0.0, max_depth=float("inf"), mask=None, color=None,
+                            color_step=None, encoding=RT_ENC_BGR8, disp_out=None, disp_kind=RT_DISP_PIXELS_F32, out_mask=None, valid_count=None,
+                            depth=None, depth_kind=RT_DEPTH_M_F32, points=None, points_compact=None, count=None, workspace=None,
+                            workspace_bytes=None, stream=None):
+        """disparity_to_frame plus the reprojection in one launch: (N,1,h,w) fp32 disparity in the network's pixels (+ mask) -> any of the
+        frame-geometry disparity (+ mask, count), a REP 118 depth image (RT_DEPTH_M_F32 / RT_DEPTH_MM_U16), the organised cloud
+        (N,out_h,out_w) x 16 bytes {x, y, z, rgb}, and -- one more launch, `workspace` of points_workspace_bytes -- the compact cloud with its
+        uint64 count per image.  camera: StereoCamera in the output's geometry; color: the left frames (N,out_h,color_step) uint8."""
+        if color_step is None:
+            color_step = out_w * ENC_BYTES.get(encoding, 0)
+        if workspace_bytes is None:
+            workspace_bytes = 0 if workspace is None else (workspace.numel() * workspace.element_size() if hasattr(workspace, "numel") else workspace.nbytes)
+        self.check(self.lib.rt_disparity_to_points(_ptr(disp_px), _ptr(mask), batch, h, w, out_h, out_w,
+                                                   ctypes.byref(camera) if camera is not None else None, min_depth, max_depth, _ptr(color),
+                                                   color_step, encoding, _ptr(disp_out), disp_kind, _ptr(out_mask), _ptr(valid_count), _ptr(depth),
+                                                   depth_kind, _ptr(points), _ptr(points_compact), _ptr(count), _ptr(workspace), workspace_bytes,
+                                                   stream), "rt_disparity_to_points")
 
     def corr_softargmax_pitched(self, l, r, out, batch, C, H, W, D, is_min, in_pitch, out_pitch, out_bstride=0,
                                 dtype=RT_F32, stream=None):
@@ -420,7 +454,6 @@ class ConvPlan:
 # whole-network ABI (include/rt_stereo_net.h, libnvstereo_inference.so)
 # ---------------------------------------------------------------------------------------------------
 RT_MODEL_RESNET18_2D, RT_MODEL_NVSMALL, RT_MODEL_NVTINY, RT_MODEL_RESNET18 = 0, 1, 2, 3
-RT_DISP_NET, RT_DISP_PIXELS_F32, RT_DISP_KITTI_U16 = 0, 1, 2          # rt_net_execute_frames: what `disp` receives
 RT_RESIZE_AREA_DOWN, RT_RESIZE_CV_AREA = 0, 1                         # rtFrameCall.resize
 RT_GEOM_NET, RT_GEOM_FRAME = 0, 1                                     # rtFrameCall.geometry
 MODEL_IDS = {"resnet18_2D": RT_MODEL_RESNET18_2D, "nvsmall": RT_MODEL_NVSMALL, "nvtiny": RT_MODEL_NVTINY,
@@ -439,6 +472,7 @@ NET_SYMBOLS = {
     "rt_net_execute_frames_viz": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int64, c_float,
                                           c_float, c_void_p, c_void_p, c_int, c_void_p]),
     "rt_net_execute_frames_ex": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "rt_net_execute_frames_3d": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "rt_net_profile": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_char_p, c_size_t]),
     "rt_net_num_layers": (c_int, [c_void_p]),
     "rt_net_num_launches": (c_int, [c_void_p]),
@@ -469,6 +503,12 @@ class FrameCall(ctypes.Structure):
     _fields_ = [("struct_bytes", c_size_t), ("left_u8", c_void_p), ("right_u8", c_void_p), ("src_h", c_int), ("src_w", c_int),
                 ("src_step", c_int64), ("encoding", c_int), ("resize", c_int), ("disp", c_void_p), ("disp_kind", c_int), ("geometry", c_int),
                 ("max_diff_px", c_float), ("mask_u8", c_void_p), ("valid_count", c_void_p), ("batch", c_int)]
+
+
+class DepthCall(ctypes.Structure):
+    """rtDepthCall (include/rt_stereo_net.h)"""
+    _fields_ = [("struct_bytes", c_size_t), ("camera", StereoCamera), ("min_depth", c_float), ("max_depth", c_float), ("depth", c_void_p),
+                ("depth_kind", c_int), ("points", c_void_p), ("points_compact", c_void_p), ("count", c_void_p)]
 
 
 def pack_weights(weights, fp16=False):
@@ -664,6 +704,23 @@ class StereoNet:
         call = FrameCall(ctypes.sizeof(FrameCall) if struct_bytes is None else struct_bytes, _ptr(left_u8), _ptr(right_u8), h, w, step, encoding,
                          resize, _ptr(disp), kind, geometry, max_diff_px, _ptr(mask), _ptr(valid_count), batch)
         self.netlib.check(self.netlib.lib.rt_net_execute_frames_ex(self.handle, ctypes.byref(call), stream), "rt_net_execute_frames_ex")
+
+    def execute_frames_3d(self, left_u8, right_u8, encoding, camera, disp=None, kind=RT_DISP_PIXELS_F32, geometry=RT_GEOM_FRAME,
+                          resize=RT_RESIZE_CV_AREA, max_diff_px=-1.0, mask=None, valid_count=None, min_depth=0.0, max_depth=float("inf"),
+                          depth=None, depth_kind=RT_DEPTH_M_F32, points=None, points_compact=None, count=None, batch=1, stream=None,
+                          src_step=None, src_w=None, struct_bytes=None, depth_struct_bytes=None, no_depth_call=False):
+        """rt_net_execute_frames_3d: execute_frames_ex in frame geometry with a depth image (N,1,src_h,src_w), the organised cloud
+        (N,src_h,src_w) x 16 bytes and / or the compact cloud with its uint64 count per image beside (or, disp=None, instead of) the
+        disparity.  camera: StereoCamera, the camera's own calibration at the frame's size.  no_depth_call: pass out = NULL."""
+        h, w, step = self._frame_geometry("rt_net_execute_frames_3d", left_u8, right_u8, encoding, batch, src_step, src_w)
+        call = FrameCall(ctypes.sizeof(FrameCall) if struct_bytes is None else struct_bytes, _ptr(left_u8), _ptr(right_u8), h, w, step, encoding,
+                         resize, _ptr(disp), kind, geometry, max_diff_px, _ptr(mask), _ptr(valid_count), batch)
+        out = None
+        if not no_depth_call:
+            out = ctypes.byref(DepthCall(ctypes.sizeof(DepthCall) if depth_struct_bytes is None else depth_struct_bytes,
+                                         camera if camera is not None else StereoCamera(), min_depth, max_depth, _ptr(depth), depth_kind,
+                                         _ptr(points), _ptr(points_compact), _ptr(count)))
+        self.netlib.check(self.netlib.lib.rt_net_execute_frames_3d(self.handle, ctypes.byref(call), out, stream), "rt_net_execute_frames_3d")
 
     def set_debug(self, on=True):
         """IExecutionContext::setDebugSync: synchronise every launch and range-check the input of every fp16-pipe convolution"""

@@ -1,6 +1,8 @@
 // Whole-network C ABI (include/rt_stereo_net.h): weight-file parsing, network/engine/context life cycle.
 #include "rt_stereo_net.h"
 
+#include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -63,6 +65,8 @@ struct rtStereoNet {
     void* frame_disp = nullptr;
     void* frame_px = nullptr;                     // rt_net_execute_frames_ex, RT_GEOM_FRAME: network-geometry pixels and mask for max_batch
     void* frame_mask = nullptr;
+    void* points_ws = nullptr;                    // rt_net_execute_frames_3d: rt_disparity_to_points' workspace, grown on demand
+    size_t points_ws_bytes = 0;
     ~rtStereoNet() {
         if (context) context->destroy();
         if (engine) engine->destroy();
@@ -71,6 +75,7 @@ struct rtStereoNet {
         rt_free(frame_disp);
         rt_free(frame_px);
         rt_free(frame_mask);
+        rt_free(points_ws);
     }
 };
 
@@ -390,16 +395,38 @@ extern "C" int rt_net_execute_frames_viz(rtStereoNet* net, const void* left_u8, 
 // as they are; everything else is the same sequence with rt_preprocess_frames_u8_cv in front and / or rt_disparity_to_frame behind.
 // Whatever an op-level call can refuse is refused by the front end, before anything is written: the back end's limits are the front
 // end's, and its other arguments are checked here.
-extern "C" int rt_net_execute_frames_ex(rtStereoNet* net, const rtFrameCall* c, rtStream stream) {
-    const std::string fn = "rt_net_execute_frames_ex: ";
+// d != NULL: rt_net_execute_frames_3d -- frame geometry only, rt_disparity_to_points behind the network, c->disp optional
+namespace {
+int execute_frames_ex(const std::string& fn, rtStereoNet* net, const rtFrameCall* c, const rtDepthCall* d, rtStream stream) {
     if (!net || !net->context || !c) return fail(fn + "null pointer");
     if (c->struct_bytes != sizeof(rtFrameCall))
         return fail(fn + "struct_bytes " + std::to_string(c->struct_bytes) + " is not sizeof(rtFrameCall) = " + std::to_string(sizeof(rtFrameCall)));
-    if (!c->left_u8 || !c->right_u8 || !c->disp) return fail(fn + "null pointer");
+    if (d && d->struct_bytes != sizeof(rtDepthCall))
+        return fail(fn + "struct_bytes " + std::to_string(d->struct_bytes) + " is not sizeof(rtDepthCall) = " + std::to_string(sizeof(rtDepthCall)));
+    if (!c->left_u8 || !c->right_u8 || (!d && !c->disp)) return fail(fn + "null pointer");
     if (c->resize != RT_RESIZE_AREA_DOWN && c->resize != RT_RESIZE_CV_AREA) return fail(fn + "unknown resize " + std::to_string(c->resize));
     if (c->geometry != RT_GEOM_NET && c->geometry != RT_GEOM_FRAME) return fail(fn + "unknown geometry " + std::to_string(c->geometry));
-    if (c->disp_kind != RT_DISP_NET && c->disp_kind != RT_DISP_PIXELS_F32 && c->disp_kind != RT_DISP_KITTI_U16)
+    if ((!d || c->disp) && c->disp_kind != RT_DISP_NET && c->disp_kind != RT_DISP_PIXELS_F32 && c->disp_kind != RT_DISP_KITTI_U16)
         return fail(fn + "unknown disp_kind " + std::to_string(c->disp_kind));
+    if (d) {                                           // what only rt_disparity_to_points can refuse, so that an error writes nothing
+        constexpr float kMax = 3.402823466e38f;
+        const rtStereoCamera& k = d->camera;
+        if (c->geometry != RT_GEOM_FRAME) {
+            fail(fn + "depth and cloud exist in the camera's own geometry only: RT_GEOM_NET is not supported, use RT_GEOM_FRAME");
+            return RT_E_UNSUPPORTED;
+        }
+        if (!d->depth && !d->points && !d->points_compact && !d->count && !c->disp) return fail(fn + "no output requested");
+        if (d->depth && d->depth_kind != RT_DEPTH_M_F32 && d->depth_kind != RT_DEPTH_MM_U16)
+            return fail(fn + "unknown depth_kind " + std::to_string(d->depth_kind));
+        if (!(k.fx > 0.f && k.fx <= kMax && k.fy > 0.f && k.fy <= kMax && k.baseline > 0.f && k.baseline <= kMax))
+            return fail(fn + "fx, fy and baseline must be finite numbers > 0");
+        if (!(std::fabs(k.cx) <= kMax && std::fabs(k.cy) <= kMax && std::fabs(k.doffs) <= kMax)) return fail(fn + "cx, cy and doffs must be finite");
+        if (!(d->min_depth >= 0.f)) return fail(fn + "min_depth must be a number >= 0");
+        if (!(d->max_depth >= d->min_depth)) return fail(fn + "max_depth must be a number >= min_depth");
+        if (d->points_compact && !d->count) return fail(fn + "points_compact needs count");
+        if (((reinterpret_cast<uintptr_t>(d->points) | reinterpret_cast<uintptr_t>(d->points_compact)) & 15) != 0)
+            return fail(fn + "a cloud must start on a 16-byte boundary");
+    }
     if (c->encoding < RT_ENC_BGR8 || c->encoding > RT_ENC_RGBA8) return fail(fn + "unknown encoding " + std::to_string(c->encoding));
     if (c->max_diff_px != c->max_diff_px) return fail(fn + "max_diff_px is not a number");
     const bool check = c->max_diff_px >= 0.f;
@@ -408,11 +435,11 @@ extern "C" int rt_net_execute_frames_ex(rtStereoNet* net, const rtFrameCall* c, 
     if (batch < 1 || (int64_t)(check ? 2 : 1) * batch > net->max_batch)
         return fail(fn + "batch " + std::to_string(batch) + (check ? " with a check" : "") + " needs an engine batch of " +
                     std::to_string((int64_t)(check ? 2 : 1) * batch) + ", max_batch is " + std::to_string(net->max_batch));
-    if (c->geometry == RT_GEOM_FRAME && c->disp_kind == RT_DISP_NET) {
+    if (c->geometry == RT_GEOM_FRAME && (!d || c->disp) && c->disp_kind == RT_DISP_NET) {
         fail(fn + "RT_GEOM_FRAME needs a disparity in pixels (RT_DISP_PIXELS_F32 / RT_DISP_KITTI_U16), not RT_DISP_NET");
         return RT_E_UNSUPPORTED;
     }
-    if (c->resize == RT_RESIZE_AREA_DOWN && c->geometry == RT_GEOM_NET)
+    if (!d && c->resize == RT_RESIZE_AREA_DOWN && c->geometry == RT_GEOM_NET)
         return check ? rt_net_execute_frames_lr(net, c->left_u8, c->right_u8, c->src_h, c->src_w, c->src_step, c->encoding, c->disp, c->disp_kind,
                                                 c->mask_u8, nullptr, c->valid_count, c->max_diff_px, batch, stream)
                      : rt_net_execute_frames(net, c->left_u8, c->right_u8, c->src_h, c->src_w, c->src_step, c->encoding, c->disp, c->disp_kind, batch,
@@ -428,6 +455,17 @@ extern "C" int rt_net_execute_frames_ex(rtStereoNet* net, const rtFrameCall* c, 
         if (!net->frame_px && rt_malloc(&net->frame_px, (size_t)net->max_batch * pixels * sizeof(float)) != 0) return fail(fn + rt_last_error_string());
         if (!net->frame_mask && rt_malloc(&net->frame_mask, (size_t)net->max_batch * pixels) != 0) return fail(fn + rt_last_error_string());
     }
+    const bool compact = d && (d->points_compact || d->count);
+    if (compact) {
+        const size_t need = rt_points_workspace_bytes(net->max_batch, c->src_h, c->src_w);      // (0 for sizes the front end refuses below)
+        if (need > net->points_ws_bytes) {
+            rt_free(net->points_ws);
+            net->points_ws = nullptr;
+            net->points_ws_bytes = 0;
+            if (rt_malloc(&net->points_ws, need) != 0) return fail(fn + rt_last_error_string());
+            net->points_ws_bytes = need;
+        }
+    }
     int rc;
     if (c->resize == RT_RESIZE_CV_AREA)
         rc = rt_preprocess_frames_u8_cv(c->left_u8, c->right_u8, c->src_h, c->src_w, c->src_step, c->encoding, net->frame_in[0], net->frame_in[1], H,
@@ -441,7 +479,22 @@ extern "C" int rt_net_execute_frames_ex(rtStereoNet* net, const rtFrameCall* c, 
     if (!ok) return fail(fn + net->log.last_error);
     const float scale = net->model == RT_MODEL_RESNET18_2D ? (float)W : 1.f;            // as rt_net_execute_frames
     const int64_t n = batch * pixels;
-    if (!frame) {
+    if (d) {                                           // the frame-geometry sequence below with rt_disparity_to_points as its last step
+        const void* px = net->frame_disp;
+        const void* mask = nullptr;
+        if (check) {
+            rc = rt_lr_consistency(net->frame_disp, batch, H, W, scale, c->max_diff_px, net->frame_px, RT_DISP_PIXELS_F32, net->frame_mask, nullptr, nullptr, stream);
+            px = net->frame_px;
+            mask = net->frame_mask;
+        } else if (net->model == RT_MODEL_RESNET18_2D) {
+            rc = rt_disparity_scale(net->frame_disp, net->frame_px, n, scale, stream);
+            px = net->frame_px;
+        }
+        if (rc == 0)
+            rc = rt_disparity_to_points(px, mask, batch, H, W, c->src_h, c->src_w, &d->camera, d->min_depth, d->max_depth, c->left_u8, c->src_step,
+                                        c->encoding, c->disp, c->disp_kind, c->mask_u8, c->valid_count, d->depth, d->depth_kind, d->points,
+                                        d->points_compact, d->count, net->points_ws, net->points_ws_bytes, stream);
+    } else if (!frame) {
         if (check) rc = rt_lr_consistency(net->frame_disp, batch, H, W, scale, c->max_diff_px, c->disp, c->disp_kind, c->mask_u8, nullptr, c->valid_count, stream);
         else if (c->disp_kind == RT_DISP_NET) rc = rt_memcpy_d2d(c->disp, net->frame_disp, (size_t)n * sizeof(float), stream);
         else if (c->disp_kind == RT_DISP_PIXELS_F32) rc = rt_disparity_scale(net->frame_disp, c->disp, n, scale, stream);
@@ -461,6 +514,18 @@ extern "C" int rt_net_execute_frames_ex(rtStereoNet* net, const rtFrameCall* c, 
     if (rc == 0 && !stream) rc = rt_stream_sync(nullptr);
     if (rc != 0) return fail(fn + rt_last_error_string());
     return 0;
+}
+}  // namespace
+
+extern "C" int rt_net_execute_frames_ex(rtStereoNet* net, const rtFrameCall* call, rtStream stream) {
+    return execute_frames_ex("rt_net_execute_frames_ex: ", net, call, nullptr, stream);
+}
+
+// rt_net_execute_frames_ex in frame geometry with depth and / or a point cloud beside (or instead of) the disparity: the same launches,
+// rt_disparity_to_points in the place of rt_disparity_to_frame
+extern "C" int rt_net_execute_frames_3d(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out, rtStream stream) {
+    if (!out) return execute_frames_ex("rt_net_execute_frames_ex: ", net, call, nullptr, stream);
+    return execute_frames_ex("rt_net_execute_frames_3d: ", net, call, out, stream);
 }
 
 extern "C" int rt_net_profile(rtStereoNet* net, const void* left, const void* right, void* disp, int batch, char* buf,

@@ -545,6 +545,258 @@ disparity_to_frame_kernel(const float* __restrict__ disp, const unsigned char* _
     }
 }
 
+// disparity_to_frame_kernel's resampling followed, in registers, by the reprojection of a rectified pair (stereo_image_proc's depth image
+// and point cloud): per frame pixel (row y, column x), all fp32, contraction off, IEEE divisions:
+//   v, valid0 = what disparity_to_frame_kernel forms      den = v + doffs      ok = valid0 && den > 0 && den finite
+//   Z = fB / den  (fB = fx * baseline, formed on the host)   ok = ok && zmin <= Z <= zmax
+//   X = (((float)x - cx) / fx) * Z      Y = (((float)y - cy) / fy) * Z
+// Outputs, each optional (uniform branches on kernel arguments): the frame-geometry disparity, mask and count exactly as
+// disparity_to_frame_kernel writes them; depth (fp32 metres, NaN = no value; or uint16 millimetres, 0 = no value, a valid 0 raised to 1);
+// the organised cloud, one 16-byte record {X, Y, Z, R << 16 | G << 8 | B} per pixel (NaN coordinates where not ok, the colour always).
+// Same lane-owns-4-pixels addressing as disparity_to_frame_kernel, the 16 gathers and the 4 colour pixels issued before their first use.
+// Cloud records go through LDS so that one store instruction of the block covers 256 consecutive records (4 KB) instead of one record
+// every 64 bytes: thread t leaves its records at slots 4t .. 4t + 3 and stores slots t, 256 + t, 512 + t, 768 + t.
+// Compaction (valid points only, row-major, deterministic) without atomics and without one workgroup waiting for another:
+//   !COMPACT: a block -- a "tile" of 1024 consecutive pixels -- leaves its number of ok pixels in tile_counts[n * tiles + blockIdx.x];
+//   COMPACT (a second launch of the same grid, same `vec`): a block sums the counts of the tiles before it (strided loads, shuffles within
+//   the wave, LDS across the four waves), forms its pixels again, and places them by ballot / popcount within the wave and the waves'
+//   totals through LDS; the block of the last tile writes count[n].
+// grid = (ceil(G / 256), batch) with G = (oh*ow + 6) / 4 groups
+struct PointsArgs {
+    const float* disp; const unsigned char* mask; int H, W, oh, ow;
+    float fB, fx, fy, cx, cy, doffs, zmin, zmax;
+    const unsigned char* color; int64_t cstep; int rgb_order;
+    void* disp_out; int disp_u16; unsigned char* omask; unsigned long long* vcount;
+    void* depth; int depth_u16;
+    uint4* points;
+    unsigned* tile_counts;                             // (batch, tiles)
+    uint4* compact; unsigned long long* count;
+    int vec;
+};
+
+template <bool MASKED, int BPP, bool DWORD, bool COMPACT>      // BPP 0: no colour (rgb = 0)
+__global__ void __launch_bounds__(256)
+disparity_to_points_kernel(const PointsArgs p) {
+#pragma clang fp contract(off)
+    __shared__ uint4 s_rec[COMPACT ? 1 : 1024];
+    __shared__ int s_count[4];
+    const int n = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int H = p.H, W = p.W, oh = p.oh, ow = p.ow;
+    const int64_t plane = (int64_t)oh * ow;
+    const int64_t obase = (int64_t)n * plane;
+    const float* D = p.disp + (int64_t)n * H * W;
+    const unsigned char* M = MASKED ? p.mask + (int64_t)n * H * W : nullptr;
+    const unsigned char* C = BPP ? p.color + (int64_t)n * oh * p.cstep : nullptr;
+    const float sx = (float)W / (float)ow, sy = (float)H / (float)oh, r = (float)ow / (float)W;
+    const int a = p.vec ? (int)(obase & 3) : 0;
+    const int64_t b0 = 4 * ((int64_t)blockIdx.x * 256) - a;                    // first element of the block's tile, image-local
+    const int64_t e0 = b0 + 4 * tid;
+    const int lo = e0 < 0 ? (int)-e0 : 0;
+    const int hi = e0 + 4 <= plane ? 4 : (int)(plane - e0);                    // <= 0: no element (such lanes still vote below)
+    const bool full = p.vec && lo == 0 && hi == 4;
+    int y = 0, x = 0;
+    if (lo < hi) {
+        y = (int)((e0 + lo) / ow);
+        x = (int)((e0 + lo) - (int64_t)y * ow);
+    }
+    int prefix = 0;
+    if constexpr (COMPACT) {                           // ok pixels of the tiles before this one (loads issued with the gathers below)
+        const unsigned* tc = p.tile_counts + (int64_t)n * gridDim.x;
+        for (int i = tid; i < (int)blockIdx.x; i += 256) prefix += (int)tc[i];
+    }
+    float t[4][4], a1[4], b1[4], fx_[4], fy_[4];
+    unsigned m[4][4], rgb[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {                      // taps and loads of all four pixels first (clamped to pixel 0 for a slot without one)
+        const bool in = k >= lo && k < hi;
+        const int xx = in ? x : 0, yy = in ? y : 0;
+        int x0, x1, y0, y1;
+        frame_tap(xx, sx, W, x0, x1, a1[k]);
+        frame_tap(yy, sy, H, y0, y1, b1[k]);
+        const int64_t r0 = (int64_t)y0 * W, r1 = (int64_t)y1 * W;
+        t[k][0] = D[r0 + x0]; t[k][1] = D[r0 + x1]; t[k][2] = D[r1 + x0]; t[k][3] = D[r1 + x1];
+        if constexpr (MASKED) {
+            m[k][0] = M[r0 + x0]; m[k][1] = M[r0 + x1]; m[k][2] = M[r1 + x0]; m[k][3] = M[r1 + x1];
+        }
+        rgb[k] = 0u;
+        if constexpr (BPP != 0) {                      // the left frame's own pixel, channels in memory order B,G,R or R,G,B; alpha dropped
+            const unsigned char* px = C + (int64_t)yy * p.cstep + (int64_t)xx * BPP;
+            unsigned c0, c1, c2;
+            if constexpr (DWORD) {
+                const unsigned q = *reinterpret_cast<const unsigned*>(px);
+                c0 = q & 0xffu; c1 = (q >> 8) & 0xffu; c2 = (q >> 16) & 0xffu;
+            } else {
+                c0 = px[0]; c1 = px[1]; c2 = px[2];
+            }
+            rgb[k] = p.rgb_order ? ((c0 << 16) | (c1 << 8) | c2) : ((c2 << 16) | (c1 << 8) | c0);
+        }
+        fx_[k] = (float)xx; fy_[k] = (float)yy;
+        if (in && ++x == ow) { x = 0; y++; }
+    }
+    constexpr unsigned kNaN = 0x7fc00000u;
+    float dv[4], Z[4];
+    unsigned valid[4], ok[4];
+    uint4 rec[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const bool in = k >= lo && k < hi;
+        const float a0 = 1.f - a1[k], bb0 = 1.f - b1[k];
+        const float top = t[k][0] * a0 + t[k][1] * a1[k];
+        const float bot = t[k][2] * a0 + t[k][3] * a1[k];
+        float v = (top * bb0 + bot * b1[k]) * r;
+        bool val = in;
+        if constexpr (MASKED) {
+            const int nt = (b1[k] > 0.5f ? 2 : 0) + (a1[k] > 0.5f ? 1 : 0);
+            const unsigned mn = nt == 0 ? m[k][0] : (nt == 1 ? m[k][1] : (nt == 2 ? m[k][2] : m[k][3]));
+            const float tn = nt == 0 ? t[k][0] : (nt == 1 ? t[k][1] : (nt == 2 ? t[k][2] : t[k][3]));
+            if (!(m[k][0] && m[k][1] && m[k][2] && m[k][3])) v = tn * r;
+            val = in && mn != 0;
+        }
+        const float den = v + p.doffs;
+        bool good = val && den > 0.f && den <= 3.402823466e38f;                // (false for a NaN)
+        const float z = p.fB / den;
+        good = good && z >= p.zmin && z <= p.zmax;
+        const float X = ((fx_[k] - p.cx) / p.fx) * z;
+        const float Y = ((fy_[k] - p.cy) / p.fy) * z;
+        dv[k] = v; Z[k] = z;
+        valid[k] = val ? 1u : 0u;
+        ok[k] = good ? 1u : 0u;
+        rec[k] = good ? make_uint4(__builtin_bit_cast(unsigned, X), __builtin_bit_cast(unsigned, Y), __builtin_bit_cast(unsigned, z), rgb[k]) : make_uint4(kNaN, kNaN, kNaN, rgb[k]);
+    }
+    unsigned long long bal[4];
+    int mine = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {                      // (uniform: every lane of every wave is here)
+        bal[k] = __ballot(ok[k]);
+        mine += __builtin_popcountll(bal[k]);
+    }
+    if constexpr (!COMPACT) {
+        if (p.disp_out) {                              // exactly disparity_to_frame_kernel's values and stores
+            if (p.disp_u16) {
+                unsigned short* out = static_cast<unsigned short*>(p.disp_out) + obase;
+                unsigned short ov[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const float q = rintf(dv[k] * 256.f);
+                    unsigned short o = (unsigned short)(q > 0.f ? (q < 65535.f ? q : 65535.f) : 0.f);      // NaN -> 0
+                    if (MASKED && o == 0) o = 1;
+                    ov[k] = valid[k] ? o : (unsigned short)0;
+                }
+                if (full) {
+                    *reinterpret_cast<uint2*>(out + e0) = make_uint2((unsigned)ov[0] | ((unsigned)ov[1] << 16), (unsigned)ov[2] | ((unsigned)ov[3] << 16));
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                        if (k >= lo && k < hi) out[e0 + k] = ov[k];
+                }
+            } else {
+                float* out = static_cast<float*>(p.disp_out) + obase;
+                float ov[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) ov[k] = valid[k] ? dv[k] : 0.f;
+                if (full) {
+                    *reinterpret_cast<float4*>(out + e0) = make_float4(ov[0], ov[1], ov[2], ov[3]);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                        if (k >= lo && k < hi) out[e0 + k] = ov[k];
+                }
+            }
+        }
+        if (MASKED && p.omask) {
+            unsigned char* om = p.omask + obase;
+            if (full) {
+                *reinterpret_cast<unsigned*>(om + e0) = (valid[0] | (valid[1] << 8) | (valid[2] << 16) | (valid[3] << 24)) * 255u;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                    if (k >= lo && k < hi) om[e0 + k] = (unsigned char)(valid[k] * 255u);
+            }
+        }
+        if (p.depth) {
+            if (p.depth_u16) {
+                unsigned short* out = static_cast<unsigned short*>(p.depth) + obase;
+                unsigned short ov[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const float q = rintf(Z[k] * 1000.f);
+                    unsigned short o = (unsigned short)(q > 0.f ? (q < 65535.f ? q : 65535.f) : 0.f);
+                    if (o == 0) o = 1;
+                    ov[k] = ok[k] ? o : (unsigned short)0;
+                }
+                if (full) {
+                    *reinterpret_cast<uint2*>(out + e0) = make_uint2((unsigned)ov[0] | ((unsigned)ov[1] << 16), (unsigned)ov[2] | ((unsigned)ov[3] << 16));
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                        if (k >= lo && k < hi) out[e0 + k] = ov[k];
+                }
+            } else {
+                unsigned* out = static_cast<unsigned*>(p.depth) + obase;
+                unsigned ov[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) ov[k] = ok[k] ? __builtin_bit_cast(unsigned, Z[k]) : kNaN;
+                if (full) {
+                    *reinterpret_cast<uint4*>(out + e0) = make_uint4(ov[0], ov[1], ov[2], ov[3]);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                        if (k >= lo && k < hi) out[e0 + k] = ov[k];
+                }
+            }
+        }
+        if (p.points) {                                // (uniform: the barrier is reached by every thread or by none)
+#pragma unroll
+            for (int k = 0; k < 4; k++) s_rec[4 * tid + k] = rec[k];
+            __syncthreads();
+            uint4* P = p.points + obase;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int64_t e = b0 + 256 * j + tid;
+                if (e >= 0 && e < plane) P[e] = s_rec[256 * j + tid];
+            }
+        }
+        if (p.tile_counts || (MASKED && p.vcount)) {   // (uniform)
+            int c = 0;
+            if (MASKED && p.vcount) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) c += __builtin_popcountll(__ballot(valid[k]));
+            }
+            if (lane == 0) s_count[wave] = p.tile_counts ? mine | (c << 12) : c;          // both at most 256 < 2^12 per wave
+            __syncthreads();
+            if (tid == 0) {
+                if (p.tile_counts) {
+                    p.tile_counts[(int64_t)n * gridDim.x + blockIdx.x] =
+                        (unsigned)((s_count[0] & 0xfff) + (s_count[1] & 0xfff) + (s_count[2] & 0xfff) + (s_count[3] & 0xfff));
+                    c = (s_count[0] >> 12) + (s_count[1] >> 12) + (s_count[2] >> 12) + (s_count[3] >> 12);
+                } else {
+                    c = s_count[0] + s_count[1] + s_count[2] + s_count[3];
+                }
+                if (MASKED && p.vcount && c) atomicAdd(p.vcount + n, (unsigned long long)c);               // one atomic per block
+            }
+        }
+    } else {
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) prefix += __shfl(prefix, lane ^ s);
+        __shared__ int s_prefix[4];
+        if (lane == 0) { s_prefix[wave] = prefix; s_count[wave] = mine; }
+        __syncthreads();
+        int pos = s_prefix[0] + s_prefix[1] + s_prefix[2] + s_prefix[3];
+        const int total = pos + s_count[0] + s_count[1] + s_count[2] + s_count[3];
+        for (int w = 0; w < wave; w++) pos += s_count[w];
+        const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+        for (int k = 0; k < 4; k++) pos += __builtin_popcountll(bal[k] & below);
+        if (p.compact) {
+            uint4* P = p.compact + obase;
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (ok[k]) P[pos++] = rec[k];
+        }
+        if (p.count && blockIdx.x == gridDim.x - 1 && tid == 0) p.count[n] = (unsigned long long)total;
+    }
+}
+
 // The viz node's 2x2 debug panel (reference ros/packages/stereo_dnn_ros_viz/src/stereo_dnn_ros_viz_node.cpp:27-130), rgb8:
 //   top-left  left frame, area-resized      top-right    right frame, area-resized
 //   bottom-left  disparity as grey          bottom-right disparity in the KITTI colour scheme (dispToColor, :49-79)

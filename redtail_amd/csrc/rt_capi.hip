@@ -744,6 +744,89 @@ extern "C" int rt_disparity_to_frame(const void* disp_px, const void* mask_u8, i
     return 0;
 }
 
+// rt_disparity_to_frame's resampling + depth + point cloud (disparity_to_points_kernel): one launch for disparity, mask, count, depth, the
+// organised cloud and the per-tile counts; one more, of the same grid, for the compact cloud and its count
+namespace {
+int64_t points_tiles(int out_h, int out_w) { return rt::cdiv(((int64_t)out_h * out_w + 3 + 3) / 4, 256); }
+}  // namespace
+
+extern "C" size_t rt_points_workspace_bytes(int batch, int out_h, int out_w) {
+    if (batch < 1 || out_h < 1 || out_w < 1) return 0;
+    return (size_t)batch * (size_t)points_tiles(out_h, out_w) * sizeof(unsigned);
+}
+
+extern "C" int rt_disparity_to_points(const void* disp_px, const void* mask_u8, int batch, int H, int W, int out_h, int out_w,
+                                      const rtStereoCamera* cam, float min_depth, float max_depth, const void* color_u8, int64_t color_step,
+                                      int encoding, void* disp_out, int disp_kind, void* out_mask_u8, void* valid_count, void* depth,
+                                      int depth_kind, void* points, void* points_compact, void* count, void* workspace,
+                                      size_t workspace_bytes, rtStream s) {
+    const char* fn = "rt_disparity_to_points";
+    constexpr float kMax = 3.402823466e38f;
+    RT_REQUIRE(disp_px && cam, "%s: null pointer", fn);
+    RT_REQUIRE(disp_out || out_mask_u8 || valid_count || depth || points || points_compact || count, "%s: no output requested", fn);
+    RT_REQUIRE(batch >= 1 && batch <= 32767 && H >= 1 && W >= 1 && out_h >= 1 && out_w >= 1 && (int64_t)H * W < ((int64_t)1 << 31) &&
+               (int64_t)out_h * out_w < ((int64_t)1 << 31), "%s: bad dims", fn);
+    RT_REQUIRE(!disp_out || disp_kind == RT_DISP_PIXELS_F32 || disp_kind == RT_DISP_KITTI_U16, "%s: unknown disp_kind %d", fn, disp_kind);
+    RT_REQUIRE(!depth || depth_kind == RT_DEPTH_M_F32 || depth_kind == RT_DEPTH_MM_U16, "%s: unknown depth_kind %d", fn, depth_kind);
+    RT_REQUIRE(mask_u8 || (!out_mask_u8 && !valid_count), "%s: out_mask_u8 and valid_count need mask_u8", fn);
+    RT_REQUIRE(cam->fx > 0.f && cam->fx <= kMax && cam->fy > 0.f && cam->fy <= kMax && cam->baseline > 0.f && cam->baseline <= kMax,
+               "%s: fx, fy and baseline must be finite numbers > 0", fn);                               // (false for NaN too)
+    RT_REQUIRE(fabsf(cam->cx) <= kMax && fabsf(cam->cy) <= kMax && fabsf(cam->doffs) <= kMax, "%s: cx, cy and doffs must be finite", fn);
+    RT_REQUIRE(min_depth >= 0.f, "%s: min_depth must be a number >= 0", fn);
+    RT_REQUIRE(max_depth >= min_depth, "%s: max_depth must be a number >= min_depth", fn);
+    int frame_bpp = 0;
+    if (color_u8) {
+        RT_REQUIRE(encoding >= RT_ENC_BGR8 && encoding <= RT_ENC_RGBA8, "%s: unknown encoding %d", fn, encoding);
+        const int bpp = frame_bpp = encoding == RT_ENC_BGRA8 || encoding == RT_ENC_RGBA8 ? 4 : 3;
+        RT_REQUIRE(color_step >= (int64_t)out_w * bpp, "%s: row step %lld is shorter than %d pixels of %d bytes", fn, (long long)color_step, out_w,
+                   bpp);
+    }
+    RT_REQUIRE(!points_compact || count, "%s: points_compact needs count", fn);
+    RT_REQUIRE(aligned16(points) && aligned16(points_compact), "%s: a cloud must start on a 16-byte boundary", fn);
+    const bool compact = points_compact || count;
+    RT_REQUIRE(!compact || (workspace && workspace_bytes >= rt_points_workspace_bytes(batch, out_h, out_w)),
+               "%s: workspace of %zu bytes, rt_points_workspace_bytes asks for %zu", fn, workspace ? workspace_bytes : (size_t)0,
+               rt_points_workspace_bytes(batch, out_h, out_w));
+    if ((float)W / out_w > 6.f || (float)H / out_h > 6.f || (float)out_w / W > 6.f || (float)out_h / H > 6.f)
+        return fail(RT_E_UNSUPPORTED, "%s: scale factors outside [1/6, 6] (%dx%d -> %dx%d) are not implemented", fn, W, H, out_w, out_h);
+    if (valid_count) RT_HIP(hipMemsetAsync(valid_count, 0, (size_t)batch * sizeof(unsigned long long), S(s)));
+    rt::PointsArgs a{};
+    a.disp = static_cast<const float*>(disp_px); a.mask = static_cast<const unsigned char*>(mask_u8);
+    a.H = H; a.W = W; a.oh = out_h; a.ow = out_w;
+    a.fB = cam->fx * cam->baseline; a.fx = cam->fx; a.fy = cam->fy; a.cx = cam->cx; a.cy = cam->cy; a.doffs = cam->doffs;
+    a.zmin = min_depth; a.zmax = max_depth;
+    a.color = static_cast<const unsigned char*>(color_u8); a.cstep = color_step;
+    a.rgb_order = encoding == RT_ENC_RGB8 || encoding == RT_ENC_RGBA8;
+    a.disp_out = disp_out; a.disp_u16 = disp_kind == RT_DISP_KITTI_U16;
+    a.omask = static_cast<unsigned char*>(out_mask_u8); a.vcount = static_cast<unsigned long long*>(valid_count);
+    a.depth = depth; a.depth_u16 = depth_kind == RT_DEPTH_MM_U16;
+    a.points = static_cast<uint4*>(points);
+    a.tile_counts = compact ? static_cast<unsigned*>(workspace) : nullptr;
+    a.compact = static_cast<uint4*>(points_compact); a.count = static_cast<unsigned long long*>(count);
+    // 16-byte (fp32) / 8-byte (16-bit) stores need those outputs 16-byte aligned, the mask's 4-byte stores the mask 4-byte aligned
+    a.vec = aligned16(disp_out) && aligned16(depth) && (reinterpret_cast<uintptr_t>(out_mask_u8) & 3) == 0;
+    const bool dword = frame_bpp == 4 && ((reinterpret_cast<uintptr_t>(color_u8) | (uintptr_t)color_step) & 3) == 0;
+    const dim3 grid((unsigned)points_tiles(out_h, out_w), (unsigned)batch);
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, S(s), a); };
+    auto pick = [&](auto masked, auto second) {
+        constexpr bool M = decltype(masked)::value, C = decltype(second)::value;
+        const int bpp = (C ? points_compact : points) ? frame_bpp : 0;          // colour only travels in a cloud
+        if (bpp == 0) launch(rt::disparity_to_points_kernel<M, 0, false, C>);
+        else if (bpp == 3) launch(rt::disparity_to_points_kernel<M, 3, false, C>);
+        else if (dword) launch(rt::disparity_to_points_kernel<M, 4, true, C>);
+        else launch(rt::disparity_to_points_kernel<M, 4, false, C>);
+    };
+    if (mask_u8) pick(std::true_type{}, std::false_type{});
+    else pick(std::false_type{}, std::false_type{});
+    RT_LAUNCH_CHECK("disparity_to_points_kernel");
+    if (compact) {
+        if (mask_u8) pick(std::true_type{}, std::true_type{});
+        else pick(std::false_type{}, std::true_type{});
+        RT_LAUNCH_CHECK("disparity_to_points_kernel (compaction)");
+    }
+    return 0;
+}
+
 // left-right consistency check + mask + output encoding of a (2 batch, 1, H, W) engine output (lr_consistency_kernel)
 extern "C" int rt_lr_consistency(const void* net_disp, int batch, int H, int W, float scale, float max_diff_px, void* out, int out_kind,
                                  void* mask_u8, void* right_out, void* valid_count, rtStream s) {
