@@ -302,6 +302,48 @@ int rt_disparity_to_points(const void* disp_px, const void* mask_u8, int batch, 
                            int encoding, void* disp_out, int disp_kind, void* out_mask_u8, void* valid_count, void* depth, int depth_kind,
                            void* points, void* points_compact, void* count, void* workspace, size_t workspace_bytes, rtStream stream);
 
+/* ---- raw frames in: rectification (image_proc's stage in front of stereo_image_proc; the reference node subscribes to image_rect_color) -- */
+/* One camera of the rig, from its sensor_msgs/CameraInfo (all float64 there). */
+typedef struct rtRectifyCamera {
+    double fx, fy, cx, cy;   /* K[0], K[4], K[2], K[5]; skew K[1] is ignored, as OpenCV's initUndistortRectifyMap ignores it */
+    double d[8];             /* k1 k2 p1 p2 k3 k4 k5 k6: plumb_bob = the first five, rest 0; rational_polynomial = all eight */
+    double iR[9];            /* inverse of P[:, :3] * R, row-major */
+} rtRectifyCamera;
+/* Host only: K, R row-major 3x3, P row-major 3x4, D the n_d first coefficients in the order of d (0, 4, 5 or 8 of them, the rest 0).  iR is a
+ * 3x3 inverse in double.  Another n_d, a non-finite entry, a singular P[:, :3] * R: error, *out untouched. */
+int rt_rectify_camera_from_info(const double K[9], const double* D, int n_d, const double R[9], const double P[12], rtRectifyCamera* out);
+/* Raw frames -> rectified frames, both frames of a pair batch in one launch.  Frames are addressed exactly as rt_preprocess_frames_u8
+ * addresses them (RT_ENC_*, rows `step` bytes apart, frame n at n * h * step); the output keeps the input's encoding and bytes per pixel;
+ * for the 4-byte encodings alpha is interpolated like a colour channel (as cv::remap treats a 4-channel Mat); bytes between a row's last
+ * pixel and dst_step are not touched.  One camera pair serves the whole batch.  Source and destination must not overlap.
+ * The map: cv::initUndistortRectifyMap's model evaluated per pixel.  For destination row v and column u, taken as doubles, everything in
+ * double, every operation rounded on its own (nothing contracted, IEEE division), in exactly this order:
+ *   X = (iR[0]*u + iR[1]*v) + iR[2]     Y = (iR[3]*u + iR[4]*v) + iR[5]     W = (iR[6]*u + iR[7]*v) + iR[8]
+ *   x = X / W,  y = Y / W,  x2 = x*x,  y2 = y*y,  r2 = x2 + y2,  xy2 = (2*x)*y
+ *   kr = (1 + ((k3*r2 + k2)*r2 + k1)*r2) / (1 + ((k6*r2 + k5)*r2 + k4)*r2)
+ *   xd = (x*kr + p1*xy2) + p2*(r2 + 2*x2)          yd = (y*kr + p1*(r2 + 2*y2)) + p2*xy2
+ *   mx = (float)(fx*xd + cx)                       my = (float)(fy*yd + cy)
+ * (OpenCV accumulates X, Y, W along the row and so differs in the last bits; this statement is the target, not OpenCV's bits.)
+ * The sampler: cv::remap(INTER_LINEAR, BORDER_CONSTANT, 0) in fp32, every operation rounded on its own.  A pixel is inside iff
+ * mx > -1 && mx < src_w && my > -1 && my < src_h, compared in fp32 before anything is made an integer (a NaN fails it); a pixel that is
+ * not inside has every byte 0.  Otherwise x0 = floorf(mx), a = mx - x0, y0 = floorf(my), b = my - y0, a tap outside the source image has
+ * the value 0, and per channel
+ *   top = S00*(1-a) + S01*a,   bot = S10*(1-a) + S11*a,   v = top*(1-b) + bot*b,   byte = rintf(v)
+ * (fp32 weights, where cv::remap rounds them to 5 fractional bits.)
+ * rt_rectify_maps writes (mx, my) of one camera as two (dst_h, dst_w) fp32 planes, the CV_32FC1 pair of initUndistortRectifyMap;
+ * rt_remap_frames_u8 is the sampler on maps of the caller (shared by the batch; any model, a fisheye one included).
+ * rt_rectify_frames_u8 is by definition rt_rectify_maps for each camera followed by rt_remap_frames_u8, bit for bit; it forms the
+ * positions in registers and never writes a map.
+ * Errors, found before anything is written: null pointers; an unknown encoding; a step (source or destination) shorter than a row; a
+ * size < 1; a non-finite field of a camera; left_dst == left_u8 or right_dst == right_u8. */
+int rt_rectify_frames_u8(const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step, int encoding,
+                         const rtRectifyCamera* cam_left, const rtRectifyCamera* cam_right,
+                         void* left_dst, void* right_dst, int dst_h, int dst_w, int64_t dst_step, int batch, rtStream stream);
+int rt_rectify_maps(const rtRectifyCamera* cam, int dst_h, int dst_w, void* map_x_f32, void* map_y_f32, rtStream stream);
+int rt_remap_frames_u8(const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step, int encoding,
+                       const void* map_x_left, const void* map_y_left, const void* map_x_right, const void* map_y_right,
+                       void* left_dst, void* right_dst, int dst_h, int dst_w, int64_t dst_step, int batch, rtStream stream);
+
 /* ---- the viz node's debug panel (ros/packages/stereo_dnn_ros_viz/src/stereo_dnn_ros_viz_node.cpp) ---------------------------- */
 /* KITTI colour scheme of the viz node's dispToColor (:49-79): disp_px (n,1,H,W) fp32 pixels -> rgb8, rows dst_step >= 3W bytes apart,
  * images H * dst_step bytes apart; bytes between 3W and dst_step are not touched.  With the reference's fp32 tables

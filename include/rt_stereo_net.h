@@ -165,6 +165,27 @@ typedef struct rtDepthCall {
 } rtDepthCall;
 int rt_net_execute_frames_3d(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out, rtStream stream);
 
+/* RAW camera frames in: rectification in front of rt_net_execute_frames_3d (rt_net_execute_frames_ex with out == NULL).
+ * call->left_u8 / right_u8 are raw frames (image_raw).  One rt_rectify_frames_u8 launch (rt_stereo.h, where map and sampler are defined)
+ * makes rectified frames of the same size and encoding -- dense buffers the net owns, made on first use for max_batch and regrown when a
+ * larger frame arrives, or the caller's left_rect_u8 / right_rect_u8 (image_rect_color), rows rect_step bytes apart -- and the call then
+ * is rt_net_execute_frames_3d(net, &call2, out, stream) with call2 = *call, its frame pointers and step replaced by the rectified ones.
+ * Composition is the definition: every output is bit-identical to those two calls made by hand, the cloud's colour is the rectified
+ * left pixel, out->camera is the calibration P describes, and whatever the wrapped call refuses is refused here.  All checks of all three
+ * structs are made before the first launch, so an error writes nothing.  Also refused: a wrong struct_bytes, one of left_rect_u8 /
+ * right_rect_u8 without the other, a rect_step shorter than a row (or not 0 with NULL), a non-finite camera field, a rectified buffer
+ * that is the raw one.  The rectify launch runs outside the engine's graph, so every pointer may rotate in graph mode; stream == NULL:
+ * synchronous. */
+typedef struct rtRectifyCall {
+    size_t struct_bytes;                 /* sizeof(rtRectifyCall) */
+    rtRectifyCamera left, right;
+    void* left_rect_u8;                  /* optional: receive the rectified frames (image_rect_color), src_h x src_w, call->encoding ... */
+    void* right_rect_u8;                 /* ... both or neither; NULL: buffers the net owns */
+    int64_t rect_step;                   /* row step of those two; 0 with NULL */
+} rtRectifyCall;
+int rt_net_execute_frames_raw(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out /* or NULL */, const rtRectifyCall* rect,
+                              rtStream stream);
+
 /* Per-launch timing through nvinfer1::IProfiler (single stream, one event pair per launch):
  * writes "name<TAB>milliseconds\n" lines into buf.  Returns 0 or an error. */
 int rt_net_profile(rtStereoNet* net, const void* left, const void* right, void* disp, int batch, char* buf,

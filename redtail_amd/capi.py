@@ -6,7 +6,7 @@ missing, or no GPU is visible, loading fails loudly.
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # RT_LIB_DIR: another build of the two libraries (redtail_amd/build.py: build_variant) for A/B measurements with bench.py / tools
@@ -40,6 +40,27 @@ class StereoCamera(ctypes.Structure):
     """rtStereoCamera (include/rt_stereo.h): a rectified pair in the geometry of the output; from sensor_msgs/CameraInfo fx = P[0], fy = P[5],
     cx = P[2], cy = P[6] of the left camera, baseline = -P_right[3] / P_right[0] (metres), doffs = P_right[2] - P_left[2] (pixels)"""
     _fields_ = [(n, c_float) for n in ("fx", "fy", "cx", "cy", "baseline", "doffs")]
+
+
+class RectifyCamera(ctypes.Structure):
+    """rtRectifyCamera (include/rt_stereo.h): one camera of a raw rig.  d: k1 k2 p1 p2 k3 k4 k5 k6; iR: inverse of P[:, :3] * R"""
+    _fields_ = [("fx", c_double), ("fy", c_double), ("cx", c_double), ("cy", c_double), ("d", c_double * 8), ("iR", c_double * 9)]
+
+    @classmethod
+    def from_camera_info(cls, K, D, R, P, lib=None):
+        """from the fields of a sensor_msgs/CameraInfo (K, R: 9 values, P: 12, D: 0, 4, 5 or 8) through rt_rectify_camera_from_info of
+        `lib` (a KernelLib; default: the product library)"""
+        import numpy as np
+        k, r, pm = (np.ascontiguousarray(np.asarray(a, np.float64).reshape(-1)) for a in (K, R, P))
+        dd = np.ascontiguousarray(np.asarray(D if D is not None else [], np.float64).reshape(-1))
+        if k.size != 9 or r.size != 9 or pm.size != 12:
+            raise ValueError("K and R hold 9 values, P holds 12")
+        lib = lib if lib is not None else KernelLib()
+        cam = cls()
+        as_p = lambda a: a.ctypes.data_as(POINTER(c_double))
+        lib.check(lib.lib.rt_rectify_camera_from_info(as_p(k), as_p(dd) if dd.size else None, int(dd.size), as_p(r), as_p(pm), ctypes.byref(cam)),
+                  "rt_rectify_camera_from_info")
+        return cam
 
 
 class Conv3dDesc(ctypes.Structure):
@@ -110,6 +131,13 @@ KERNEL_SYMBOLS = {
     "rt_disparity_to_points": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(StereoCamera), c_float, c_float, c_void_p,
                                        c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_size_t, c_void_p]),
+    "rt_rectify_camera_from_info": (c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), POINTER(c_double),
+                                            POINTER(RectifyCamera)]),
+    "rt_rectify_frames_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, POINTER(RectifyCamera), POINTER(RectifyCamera), c_void_p,
+                                     c_void_p, c_int, c_int, c_int64, c_int, c_void_p]),
+    "rt_rectify_maps": (c_int, [POINTER(RectifyCamera), c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "rt_remap_frames_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_int, c_int, c_int64, c_int, c_void_p]),
     "rt_disparity_to_color": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p]),
     "rt_viz_mosaic_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_int64, c_int,
                                  c_void_p]),
@@ -258,6 +286,27 @@ class KernelLib:
         pixels, `kind` RT_DISP_PIXELS_F32 or RT_DISP_KITTI_U16; with a mask: the frame's uint8 mask and uint64 count per image"""
         self.check(self.lib.rt_disparity_to_frame(_ptr(disp_px), _ptr(mask), batch, h, w, _ptr(out), kind, out_h, out_w, _ptr(out_mask),
                                                   _ptr(valid_count), stream), "rt_disparity_to_frame")
+
+    def rectify_frames_u8(self, left, right, src_h, src_w, src_step, encoding, cam_left, cam_right, left_dst, right_dst, dst_h, dst_w,
+                          dst_step, batch=1, stream=None):
+        """raw frames -> rectified frames of the same encoding, both frames of a pair batch in one launch: initUndistortRectifyMap's model
+        per pixel in double, remap(INTER_LINEAR, BORDER_CONSTANT 0) in fp32.  cam_left / cam_right: RectifyCamera"""
+        self.check(self.lib.rt_rectify_frames_u8(_ptr(left), _ptr(right), src_h, src_w, src_step, encoding,
+                                                 ctypes.byref(cam_left) if cam_left is not None else None,
+                                                 ctypes.byref(cam_right) if cam_right is not None else None, _ptr(left_dst), _ptr(right_dst),
+                                                 dst_h, dst_w, dst_step, batch, stream), "rt_rectify_frames_u8")
+
+    def rectify_maps(self, cam, dst_h, dst_w, map_x, map_y, stream=None):
+        """the (dst_h, dst_w) fp32 map pair of one RectifyCamera, as rectify_frames_u8 forms it in registers"""
+        self.check(self.lib.rt_rectify_maps(ctypes.byref(cam) if cam is not None else None, dst_h, dst_w, _ptr(map_x), _ptr(map_y), stream),
+                   "rt_rectify_maps")
+
+    def remap_frames_u8(self, left, right, src_h, src_w, src_step, encoding, map_x_left, map_y_left, map_x_right, map_y_right, left_dst,
+                        right_dst, dst_h, dst_w, dst_step, batch=1, stream=None):
+        """rectify_frames_u8's sampler on the caller's own maps (shared by the batch)"""
+        self.check(self.lib.rt_remap_frames_u8(_ptr(left), _ptr(right), src_h, src_w, src_step, encoding, _ptr(map_x_left), _ptr(map_y_left),
+                                               _ptr(map_x_right), _ptr(map_y_right), _ptr(left_dst), _ptr(right_dst), dst_h, dst_w, dst_step,
+                                               batch, stream), "rt_remap_frames_u8")
 
     def points_workspace_bytes(self, batch, out_h, out_w):
         """bytes of device workspace disparity_to_points needs for a compact cloud or a count"""
@@ -473,6 +522,7 @@ NET_SYMBOLS = {
                                           c_float, c_void_p, c_void_p, c_int, c_void_p]),
     "rt_net_execute_frames_ex": (c_int, [c_void_p, c_void_p, c_void_p]),
     "rt_net_execute_frames_3d": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rt_net_execute_frames_raw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rt_net_profile": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_char_p, c_size_t]),
     "rt_net_num_layers": (c_int, [c_void_p]),
     "rt_net_num_launches": (c_int, [c_void_p]),
@@ -509,6 +559,12 @@ class DepthCall(ctypes.Structure):
     """rtDepthCall (include/rt_stereo_net.h)"""
     _fields_ = [("struct_bytes", c_size_t), ("camera", StereoCamera), ("min_depth", c_float), ("max_depth", c_float), ("depth", c_void_p),
                 ("depth_kind", c_int), ("points", c_void_p), ("points_compact", c_void_p), ("count", c_void_p)]
+
+
+class RectifyCall(ctypes.Structure):
+    """rtRectifyCall (include/rt_stereo_net.h)"""
+    _fields_ = [("struct_bytes", c_size_t), ("left", RectifyCamera), ("right", RectifyCamera), ("left_rect_u8", c_void_p),
+                ("right_rect_u8", c_void_p), ("rect_step", c_int64)]
 
 
 def pack_weights(weights, fp16=False):
@@ -721,6 +777,30 @@ class StereoNet:
                                          camera if camera is not None else StereoCamera(), min_depth, max_depth, _ptr(depth), depth_kind,
                                          _ptr(points), _ptr(points_compact), _ptr(count)))
         self.netlib.check(self.netlib.lib.rt_net_execute_frames_3d(self.handle, ctypes.byref(call), out, stream), "rt_net_execute_frames_3d")
+
+    def execute_frames_raw(self, left_u8, right_u8, encoding, rect_left, rect_right, camera=None, disp=None, kind=RT_DISP_PIXELS_F32,
+                           geometry=RT_GEOM_FRAME, resize=RT_RESIZE_CV_AREA, max_diff_px=-1.0, mask=None, valid_count=None, min_depth=0.0,
+                           max_depth=float("inf"), depth=None, depth_kind=RT_DEPTH_M_F32, points=None, points_compact=None, count=None, batch=1,
+                           stream=None, src_step=None, src_w=None, struct_bytes=None, depth_struct_bytes=None, no_depth_call=False,
+                           left_rect=None, right_rect=None, rect_step=None, rect_struct_bytes=None):
+        """rt_net_execute_frames_raw: RAW frames in.  One rectify_frames_u8 launch with the RectifyCameras rect_left / rect_right into
+        rectified frames of the same size and encoding (buffers of the net, or left_rect / right_rect: (N, H, rect_step) uint8, rect_step
+        defaulting to their row stride), then execute_frames_3d on them with the same keywords (no_depth_call: execute_frames_ex)."""
+        h, w, step = self._frame_geometry("rt_net_execute_frames_raw", left_u8, right_u8, encoding, batch, src_step, src_w)
+        call = FrameCall(ctypes.sizeof(FrameCall) if struct_bytes is None else struct_bytes, _ptr(left_u8), _ptr(right_u8), h, w, step, encoding,
+                         resize, _ptr(disp), kind, geometry, max_diff_px, _ptr(mask), _ptr(valid_count), batch)
+        out = None
+        if not no_depth_call:
+            out = ctypes.byref(DepthCall(ctypes.sizeof(DepthCall) if depth_struct_bytes is None else depth_struct_bytes,
+                                         camera if camera is not None else StereoCamera(), min_depth, max_depth, _ptr(depth), depth_kind,
+                                         _ptr(points), _ptr(points_compact), _ptr(count)))
+        if rect_step is None:
+            given = left_rect if left_rect is not None else right_rect
+            rect_step = 0 if given is None else (given.stride(1) if hasattr(given, "data_ptr") else given.strides[1])
+        rect = RectifyCall(ctypes.sizeof(RectifyCall) if rect_struct_bytes is None else rect_struct_bytes, rect_left, rect_right,
+                           _ptr(left_rect), _ptr(right_rect), rect_step)
+        self.netlib.check(self.netlib.lib.rt_net_execute_frames_raw(self.handle, ctypes.byref(call), out, ctypes.byref(rect), stream),
+                          "rt_net_execute_frames_raw")
 
     def set_debug(self, on=True):
         """IExecutionContext::setDebugSync: synchronise every launch and range-check the input of every fp16-pipe convolution"""

@@ -67,6 +67,8 @@ struct rtStereoNet {
     void* frame_mask = nullptr;
     void* points_ws = nullptr;                    // rt_net_execute_frames_3d: rt_disparity_to_points' workspace, grown on demand
     size_t points_ws_bytes = 0;
+    void* rect[2] = {nullptr, nullptr};           // rt_net_execute_frames_raw: dense rectified frames for max_batch, grown on demand
+    size_t rect_bytes = 0;
     ~rtStereoNet() {
         if (context) context->destroy();
         if (engine) engine->destroy();
@@ -76,6 +78,8 @@ struct rtStereoNet {
         rt_free(frame_px);
         rt_free(frame_mask);
         rt_free(points_ws);
+        rt_free(rect[0]);
+        rt_free(rect[1]);
     }
 };
 
@@ -396,9 +400,13 @@ extern "C" int rt_net_execute_frames_viz(rtStereoNet* net, const void* left_u8, 
 // Whatever an op-level call can refuse is refused by the front end, before anything is written: the back end's limits are the front
 // end's, and its other arguments are checked here.
 // d != NULL: rt_net_execute_frames_3d -- frame geometry only, rt_disparity_to_points behind the network, c->disp optional
+// r != NULL: rt_net_execute_frames_raw -- c's frames are raw; one rt_rectify_frames_u8 launch in front, everything else on its output
 namespace {
-int execute_frames_ex(const std::string& fn, rtStereoNet* net, const rtFrameCall* c, const rtDepthCall* d, rtStream stream) {
+int execute_frames_ex(const std::string& fn, rtStereoNet* net, const rtFrameCall* c, const rtDepthCall* d, const rtRectifyCall* r,
+                      rtStream stream) {
     if (!net || !net->context || !c) return fail(fn + "null pointer");
+    if (r && r->struct_bytes != sizeof(rtRectifyCall))
+        return fail(fn + "struct_bytes " + std::to_string(r->struct_bytes) + " is not sizeof(rtRectifyCall) = " + std::to_string(sizeof(rtRectifyCall)));
     if (c->struct_bytes != sizeof(rtFrameCall))
         return fail(fn + "struct_bytes " + std::to_string(c->struct_bytes) + " is not sizeof(rtFrameCall) = " + std::to_string(sizeof(rtFrameCall)));
     if (d && d->struct_bytes != sizeof(rtDepthCall))
@@ -438,6 +446,59 @@ int execute_frames_ex(const std::string& fn, rtStereoNet* net, const rtFrameCall
     if (c->geometry == RT_GEOM_FRAME && (!d || c->disp) && c->disp_kind == RT_DISP_NET) {
         fail(fn + "RT_GEOM_FRAME needs a disparity in pixels (RT_DISP_PIXELS_F32 / RT_DISP_KITTI_U16), not RT_DISP_NET");
         return RT_E_UNSUPPORTED;
+    }
+    rtFrameCall rectified;
+    if (r) {
+        // What the front end and rt_rectify_frames_u8 would refuse, found here: behind the rectify launch an error could no longer
+        // write nothing.  (The back end's limits are the front end's.)
+        const int H = net->height, W = net->width;
+        const int bpp = c->encoding == RT_ENC_BGRA8 || c->encoding == RT_ENC_RGBA8 ? 4 : 3;
+        if (c->src_h < 1 || c->src_w < 1 || c->src_h > (1 << 24) || c->src_w > (1 << 24) || (int64_t)c->src_h * c->src_w >= ((int64_t)1 << 31) ||
+            batch > 32767)
+            return fail(fn + "bad dims");
+        if (c->src_step < (int64_t)c->src_w * bpp)
+            return fail(fn + "row step " + std::to_string(c->src_step) + " is shorter than " + std::to_string(c->src_w) + " pixels of " +
+                        std::to_string(bpp) + " bytes");
+        const bool down = H <= c->src_h && W <= c->src_w;
+        if (c->resize == RT_RESIZE_AREA_DOWN && !down)
+            return fail(fn + "INTER_AREA up-scaling (" + std::to_string(c->src_w) + "x" + std::to_string(c->src_h) + " -> " + std::to_string(W) + "x" +
+                        std::to_string(H) + ") is not implemented by RT_RESIZE_AREA_DOWN");
+        if ((float)c->src_w / W > 6.f || (float)c->src_h / H > 6.f || (float)W / c->src_w > 6.f || (float)H / c->src_h > 6.f)
+            return fail(fn + "scale factors outside [1/6, 6] are not implemented");
+        if (!r->left_rect_u8 != !r->right_rect_u8) return fail(fn + "left_rect_u8 and right_rect_u8: both or neither");
+        if (r->left_rect_u8 ? r->rect_step < (int64_t)c->src_w * bpp : r->rect_step != 0)
+            return fail(fn + "rect_step " + std::to_string(r->rect_step) + (r->left_rect_u8 ? " is shorter than a row" : " without buffers"));
+        for (const rtRectifyCamera* k : {&r->left, &r->right}) {
+            const double* v = reinterpret_cast<const double*>(k);
+            for (size_t i = 0; i < sizeof(rtRectifyCamera) / sizeof(double); i++)
+                if (!std::isfinite(v[i])) return fail(fn + "every field of a camera must be finite");
+        }
+        if (r->left_rect_u8 == c->left_u8 || r->right_rect_u8 == c->right_u8) return fail(fn + "a rectified buffer must not be the raw one");
+        rectified = *c;
+        if (r->left_rect_u8) {
+            rectified.left_u8 = r->left_rect_u8;
+            rectified.right_u8 = r->right_rect_u8;
+            rectified.src_step = r->rect_step;
+        } else {
+            const size_t need = (size_t)net->max_batch * c->src_h * c->src_w * bpp;
+            if (need > net->rect_bytes) {
+                for (void*& p : net->rect) {
+                    rt_free(p);
+                    p = nullptr;
+                }
+                net->rect_bytes = 0;
+                if (rt_malloc(&net->rect[0], need) != 0 || rt_malloc(&net->rect[1], need) != 0) return fail(fn + rt_last_error_string());
+                net->rect_bytes = need;
+            }
+            rectified.left_u8 = net->rect[0];
+            rectified.right_u8 = net->rect[1];
+            rectified.src_step = (int64_t)c->src_w * bpp;
+        }
+        if (rt_rectify_frames_u8(c->left_u8, c->right_u8, c->src_h, c->src_w, c->src_step, c->encoding, &r->left, &r->right,
+                                 const_cast<void*>(rectified.left_u8), const_cast<void*>(rectified.right_u8), c->src_h, c->src_w, rectified.src_step,
+                                 batch, stream) != 0)
+            return fail(fn + rt_last_error_string());
+        c = &rectified;
     }
     if (!d && c->resize == RT_RESIZE_AREA_DOWN && c->geometry == RT_GEOM_NET)
         return check ? rt_net_execute_frames_lr(net, c->left_u8, c->right_u8, c->src_h, c->src_w, c->src_step, c->encoding, c->disp, c->disp_kind,
@@ -518,14 +579,21 @@ int execute_frames_ex(const std::string& fn, rtStereoNet* net, const rtFrameCall
 }  // namespace
 
 extern "C" int rt_net_execute_frames_ex(rtStereoNet* net, const rtFrameCall* call, rtStream stream) {
-    return execute_frames_ex("rt_net_execute_frames_ex: ", net, call, nullptr, stream);
+    return execute_frames_ex("rt_net_execute_frames_ex: ", net, call, nullptr, nullptr, stream);
 }
 
 // rt_net_execute_frames_ex in frame geometry with depth and / or a point cloud beside (or instead of) the disparity: the same launches,
 // rt_disparity_to_points in the place of rt_disparity_to_frame
 extern "C" int rt_net_execute_frames_3d(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out, rtStream stream) {
-    if (!out) return execute_frames_ex("rt_net_execute_frames_ex: ", net, call, nullptr, stream);
-    return execute_frames_ex("rt_net_execute_frames_3d: ", net, call, out, stream);
+    if (!out) return execute_frames_ex("rt_net_execute_frames_ex: ", net, call, nullptr, nullptr, stream);
+    return execute_frames_ex("rt_net_execute_frames_3d: ", net, call, out, nullptr, stream);
+}
+
+// raw frames in: one rt_rectify_frames_u8 launch, then the call above on its output
+extern "C" int rt_net_execute_frames_raw(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out, const rtRectifyCall* rect,
+                                         rtStream stream) {
+    if (!rect) return fail("rt_net_execute_frames_raw: null pointer");
+    return execute_frames_ex("rt_net_execute_frames_raw: ", net, call, out, rect, stream);
 }
 
 extern "C" int rt_net_profile(rtStereoNet* net, const void* left, const void* right, void* disp, int batch, char* buf,

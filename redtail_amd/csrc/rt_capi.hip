@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -27,6 +28,7 @@
 #include "kernels/conv_wino.hip.h"
 #include "kernels/deconv3d_small.hip.h"
 #include "kernels/imgproc.hip.h"
+#include "kernels/rectify.hip.h"
 #include "kernels/conv_f16.hip.h"
 #include "kernels/conv_f16_first.hip.h"
 #include "kernels/conv_f16r4.hip.h"
@@ -711,6 +713,123 @@ extern "C" int rt_preprocess_frames_u8_cv(const void* left, const void* right, i
         else launch(rt::preprocess_frames_cv_kernel<4, false, false>);
     }
     RT_LAUNCH_CHECK("preprocess_frames_cv_kernel");
+    return 0;
+}
+
+// Raw frames in: rectification (kernels/rectify.hip.h).  rt_rectify_frames_u8 forms the positions in registers, rt_rectify_maps writes
+// them out and rt_remap_frames_u8 reads them back: the same device function and the same sampler, so the three agree bit for bit.
+extern "C" int rt_rectify_camera_from_info(const double K[9], const double* D, int n_d, const double R[9], const double P[12],
+                                           rtRectifyCamera* out) {
+    const char* fn = "rt_rectify_camera_from_info";
+    RT_REQUIRE(K && R && P && out && (D || n_d == 0), "%s: null pointer", fn);
+    RT_REQUIRE(n_d == 0 || n_d == 4 || n_d == 5 || n_d == 8, "%s: %d distortion coefficients (0, 4, 5 or 8 are known)", fn, n_d);
+    bool finite = true;
+    for (int i = 0; i < 9; i++) finite = finite && std::isfinite(K[i]) && std::isfinite(R[i]);
+    for (int i = 0; i < 12; i++) finite = finite && std::isfinite(P[i]);
+    for (int i = 0; i < n_d; i++) finite = finite && std::isfinite(D[i]);
+    RT_REQUIRE(finite, "%s: K, D, R and P must be finite", fn);
+    double m[9];                                       // P[:, :3] * R
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) m[3 * i + j] = (P[4 * i] * R[j] + P[4 * i + 1] * R[3 + j]) + P[4 * i + 2] * R[6 + j];
+    const double c[9] = {m[4] * m[8] - m[5] * m[7], m[2] * m[7] - m[1] * m[8], m[1] * m[5] - m[2] * m[4],
+                         m[5] * m[6] - m[3] * m[8], m[0] * m[8] - m[2] * m[6], m[2] * m[3] - m[0] * m[5],
+                         m[3] * m[7] - m[4] * m[6], m[1] * m[6] - m[0] * m[7], m[0] * m[4] - m[1] * m[3]};      // the adjugate, row-major
+    const double det = (m[0] * c[0] + m[1] * c[3]) + m[2] * c[6];
+    rtRectifyCamera cam{};
+    bool ok = det != 0.0 && std::isfinite(det);
+    for (int i = 0; i < 9 && ok; i++) {
+        cam.iR[i] = c[i] / det;
+        ok = std::isfinite(cam.iR[i]);
+    }
+    RT_REQUIRE(ok, "%s: P[:, :3] * R is singular", fn);
+    cam.fx = K[0]; cam.fy = K[4]; cam.cx = K[2]; cam.cy = K[5];
+    for (int i = 0; i < n_d; i++) cam.d[i] = D[i];
+    *out = cam;
+    return 0;
+}
+
+namespace {
+static_assert(sizeof(rt::RectifyCam) == sizeof(rtRectifyCamera), "rt::RectifyCam is rtRectifyCamera field for field");
+bool rectify_camera_finite(const rtRectifyCamera* c) {
+    const double* v = reinterpret_cast<const double*>(c);
+    for (size_t i = 0; i < sizeof(rtRectifyCamera) / sizeof(double); i++)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+int rectify_launch(const char* fn, const void* left, const void* right, int src_h, int src_w, int64_t src_step, int encoding,
+                   const rtRectifyCamera* cam_left, const rtRectifyCamera* cam_right, const void* const maps[4], void* left_dst,
+                   void* right_dst, int dst_h, int dst_w, int64_t dst_step, int batch, rtStream s) {
+    const bool by_map = maps != nullptr;
+    RT_REQUIRE(left && right && left_dst && right_dst, "%s: null pointer", fn);
+    if (by_map) RT_REQUIRE(maps[0] && maps[1] && maps[2] && maps[3], "%s: null pointer", fn);
+    else RT_REQUIRE(cam_left && cam_right, "%s: null pointer", fn);
+    RT_REQUIRE(encoding >= RT_ENC_BGR8 && encoding <= RT_ENC_RGBA8, "%s: unknown encoding %d", fn, encoding);
+    RT_REQUIRE(src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0 && batch > 0 && batch <= 32767 && dst_h <= 4 * 65535 && src_h <= (1 << 24) &&
+               src_w <= (1 << 24), "%s: bad dims", fn);
+    const int bpp = encoding == RT_ENC_BGRA8 || encoding == RT_ENC_RGBA8 ? 4 : 3;
+    RT_REQUIRE(src_step >= (int64_t)src_w * bpp, "%s: row step %lld is shorter than %d pixels of %d bytes", fn, (long long)src_step, src_w, bpp);
+    RT_REQUIRE(dst_step >= (int64_t)dst_w * bpp, "%s: destination row step %lld is shorter than %d pixels of %d bytes", fn, (long long)dst_step,
+               dst_w, bpp);
+    RT_REQUIRE(by_map || (rectify_camera_finite(cam_left) && rectify_camera_finite(cam_right)), "%s: every field of a camera must be finite", fn);
+    RT_REQUIRE(left_dst != left && right_dst != right, "%s: source and destination must not overlap", fn);
+    rt::RectifyArgs a{};
+    a.left = static_cast<const unsigned char*>(left); a.right = static_cast<const unsigned char*>(right);
+    a.sh = src_h; a.sw = src_w; a.step = src_step;
+    a.dleft = static_cast<unsigned char*>(left_dst); a.dright = static_cast<unsigned char*>(right_dst);
+    a.dh = dst_h; a.dw = dst_w; a.dstep = dst_step; a.batch = batch;
+    if (by_map) {
+        a.mxl = static_cast<const float*>(maps[0]); a.myl = static_cast<const float*>(maps[1]);
+        a.mxr = static_cast<const float*>(maps[2]); a.myr = static_cast<const float*>(maps[3]);
+    } else {
+        memcpy(&a.cam[0], cam_left, sizeof(rt::RectifyCam));
+        memcpy(&a.cam[1], cam_right, sizeof(rt::RectifyCam));
+    }
+    const bool dword = bpp == 4 && ((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right) | reinterpret_cast<uintptr_t>(left_dst) |
+                                     reinterpret_cast<uintptr_t>(right_dst) | (uintptr_t)src_step | (uintptr_t)dst_step) & 3) == 0;
+    const dim3 grid((unsigned)rt::cdiv(dst_w, rt::kFramesCols), (unsigned)rt::cdiv(dst_h, rt::kFramesRows), (unsigned)(2 * batch));
+    const dim3 block(rt::kFramesCols * rt::kFramesRows);
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, S(s), a); };
+    if (by_map) {
+        if (bpp == 3) launch(rt::rectify_frames_kernel<3, false, true>);
+        else if (dword) launch(rt::rectify_frames_kernel<4, true, true>);
+        else launch(rt::rectify_frames_kernel<4, false, true>);
+    } else {
+        if (bpp == 3) launch(rt::rectify_frames_kernel<3, false, false>);
+        else if (dword) launch(rt::rectify_frames_kernel<4, true, false>);
+        else launch(rt::rectify_frames_kernel<4, false, false>);
+    }
+    RT_LAUNCH_CHECK("rectify_frames_kernel");
+    return 0;
+}
+}  // namespace
+
+extern "C" int rt_rectify_frames_u8(const void* left, const void* right, int src_h, int src_w, int64_t src_step, int encoding,
+                                    const rtRectifyCamera* cam_left, const rtRectifyCamera* cam_right, void* left_dst, void* right_dst,
+                                    int dst_h, int dst_w, int64_t dst_step, int batch, rtStream s) {
+    return rectify_launch("rt_rectify_frames_u8", left, right, src_h, src_w, src_step, encoding, cam_left, cam_right, nullptr, left_dst,
+                          right_dst, dst_h, dst_w, dst_step, batch, s);
+}
+
+extern "C" int rt_remap_frames_u8(const void* left, const void* right, int src_h, int src_w, int64_t src_step, int encoding,
+                                  const void* map_x_left, const void* map_y_left, const void* map_x_right, const void* map_y_right,
+                                  void* left_dst, void* right_dst, int dst_h, int dst_w, int64_t dst_step, int batch, rtStream s) {
+    const void* const maps[4] = {map_x_left, map_y_left, map_x_right, map_y_right};
+    return rectify_launch("rt_remap_frames_u8", left, right, src_h, src_w, src_step, encoding, nullptr, nullptr, maps, left_dst, right_dst,
+                          dst_h, dst_w, dst_step, batch, s);
+}
+
+extern "C" int rt_rectify_maps(const rtRectifyCamera* cam, int dst_h, int dst_w, void* map_x, void* map_y, rtStream s) {
+    const char* fn = "rt_rectify_maps";
+    RT_REQUIRE(cam && map_x && map_y, "%s: null pointer", fn);
+    RT_REQUIRE(dst_h > 0 && dst_w > 0 && dst_h <= 4 * 65535, "%s: bad dims", fn);
+    RT_REQUIRE(rectify_camera_finite(cam), "%s: every field of a camera must be finite", fn);
+    rt::RectifyCam c;
+    memcpy(&c, cam, sizeof(c));
+    const dim3 grid((unsigned)rt::cdiv(dst_w, rt::kFramesCols), (unsigned)rt::cdiv(dst_h, rt::kFramesRows));
+    hipLaunchKernelGGL(rt::rectify_maps_kernel, grid, dim3(rt::kFramesCols * rt::kFramesRows), 0, S(s), c, static_cast<float*>(map_x),
+                       static_cast<float*>(map_y), dst_h, dst_w);
+    RT_LAUNCH_CHECK("rectify_maps_kernel");
     return 0;
 }
 
