@@ -631,14 +631,15 @@ struct S3FirstCfg {
     static constexpr int PR = (TY - 1) * S + KH, PC = (TX - 1) * S + KW;      // 11 x 67 input pixels per channel
     static constexpr int NPAIR = (PC + 1) / 2;                                // column pairs per row: 34 (68 columns)
     static constexpr int RS = 208;                                            // LDS row stride in halfs >= 68*3 = 204, 16-byte multiple
-    static constexpr int NTASK = CMAX * PR * NPAIR, NK = (NTASK + 255) / 256; // (channel, row, pair) gathers per lane
+    static constexpr int NRUN = NPAIR / 2, NRUN_T = PR * NRUN;                // runs of 4 columns per row: 17; (row, run) gathers: 187, one per lane
+    static_assert(NPAIR % 2 == 0 && NRUN_T <= 256 && (RS * 2) % 8 == 0 && NRUN * 4 * CMAX <= RS, "one gather per lane, 8-byte LDS writes");
     static constexpr int W_SLOTS = KH * 2 * 2 * 32;                           // 16-byte slots per 32-channel block: [r][hi/lo][k-half][co]
 };
 
 template <bool YIL>
 __global__ void __launch_bounds__(256) RT_WAVES_PER_EU(4) conv_s3_first_kernel(ConvArgs p) {
     using Cfg = S3FirstCfg;
-    constexpr int KH = Cfg::KH, S = Cfg::S, TY = Cfg::TY, TX = Cfg::TX, PR = Cfg::PR, NPAIR = Cfg::NPAIR, RS = Cfg::RS;
+    constexpr int KH = Cfg::KH, S = Cfg::S, TY = Cfg::TY, TX = Cfg::TX, PR = Cfg::PR, RS = Cfg::RS;
 
     __shared__ __attribute__((aligned(16))) _Float16 sHi[PR * RS];
     __shared__ __attribute__((aligned(16))) _Float16 sLo[PR * RS];
@@ -669,30 +670,54 @@ __global__ void __launch_bounds__(256) RT_WAVES_PER_EU(4) conv_s3_first_kernel(C
             for (int part = 0; part < 2; part++) wa[r][part] = buf_load4(rs_w, (unsigned)(((r * 2 + part) * 2 + kg) * 32 + l31) * 16u, 0);
     }
 
-    // ---- gather: fp32 image -> split patches [row][col][channel]; a lane takes a column pair of one channel --------------
+    // the bias of the epilogue travels with the weights: requested behind the barrier it would be a round trip nothing hides
+    const int cb = nblk * 32;
+    f32x4 bv[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) bv[q] = *reinterpret_cast<const f32x4*>(p.bias + cb + 8 * q + 4 * kg);
+
+    // ---- gather: fp32 image -> split patches [row][col][channel]; a lane takes a run of 4 columns of one patch row, all channels -------
+    // One 16-byte load per channel (a row start is only 4-byte aligned: dense rows of an odd width) and the run's 12 halfs of each image
+    // as three 8-byte LDS writes.  A run that crosses an edge of the image row takes its elements one by one instead (the first run of
+    // the first tile column, one or two runs of the last): a branch the other waves skip.
     const buf_rsrc rs_x = make_buf((p.x2 && n >= p.x2_from) ? p.x2 + (int64_t)(n - p.x2_from) * p.x_bstride : p.x + (int64_t)n * p.x_bstride);
     const int ix0 = tx0 * S - p.pad_x, iy0 = ty0 * S - p.pad_y;
     const int cin = p.cin_real;
-#pragma unroll
-    for (int k = 0; k < Cfg::NK; k++) {
-        const int t = tid + 256 * k;
-        const int c = t / (PR * NPAIR), rem = t - c * (PR * NPAIR);
-        const int pr = rem / NPAIR, pc = 2 * (rem - pr * NPAIR);
+    if (tid < Cfg::NRUN_T) {
+        const int pr = (int)((unsigned)tid / (unsigned)Cfg::NRUN), pc = 4 * (tid - pr * Cfg::NRUN);
         const int iy = iy0 + pr, ix = ix0 + pc;
-        const bool own = t < Cfg::NTASK && c < cin;
-        const bool row_ok = own && iy >= 0 && iy < p.Hi;
-        // the pair may straddle either edge of a dense row: each element is masked on its own
-        const bool ok0 = row_ok && ix >= 0 && ix < p.Wi, ok1 = row_ok && ix + 1 >= 0 && ix + 1 < p.Wi && pc + 1 < Cfg::PC;
-        const unsigned vo = (unsigned)((c * p.Hi + iy) * p.x_pitch + ix) * 4u;
-        const float v0 = buf_load(rs_x, ok0 ? vo : kBufOOB, 0);
-        const float v1 = buf_load(rs_x, ok1 ? vo + 4u : kBufOOB, 0);
-        if (t < Cfg::NTASK) {                     // channels >= cin are written as zeros
-            const _Float16 h0 = (_Float16)v0, h1 = (_Float16)v1;
-            const int o = pr * RS + pc * Cfg::CMAX + c;
-            sHi[o] = h0;
-            sHi[o + Cfg::CMAX] = h1;
-            sLo[o] = (_Float16)((v0 - (float)h0) * kSplitScale);
-            sLo[o + Cfg::CMAX] = (_Float16)((v1 - (float)h1) * kSplitScale);
+        const bool row_ok = iy >= 0 && iy < p.Hi;
+        const bool whole = row_ok && ix >= 0 && ix + 3 < p.Wi;
+        const unsigned vo = (unsigned)(iy * p.x_pitch + ix) * 4u, cs = (unsigned)(p.Hi * p.x_pitch) * 4u;
+        f32x4 v[Cfg::CMAX];
+#pragma unroll
+        for (int c = 0; c < Cfg::CMAX; c++) v[c] = buf_load4(rs_x, (whole && c < cin) ? vo + c * cs : kBufOOB, 0);      // channels >= cin: zeros
+        if (row_ok && !whole) {
+#pragma unroll
+            for (int c = 0; c < Cfg::CMAX; c++)
+#pragma unroll
+                for (int e = 0; e < 4; e++)
+                    v[c][e] = buf_load(rs_x, (c < cin && ix + e >= 0 && ix + e < p.Wi) ? vo + c * cs + 4u * e : kBufOOB, 0);
+        }
+        if (pc + 3 >= Cfg::PC) {                  // the 68th column is padding of the patch, not image
+#pragma unroll
+            for (int c = 0; c < Cfg::CMAX; c++) v[c][3] = 0.f;
+        }
+        unsigned short hh[4 * Cfg::CMAX], ll[4 * Cfg::CMAX];
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+#pragma unroll
+            for (int c = 0; c < Cfg::CMAX; c++) {
+                const _Float16 h = (_Float16)v[c][e];
+                hh[e * Cfg::CMAX + c] = __builtin_bit_cast(unsigned short, h);
+                ll[e * Cfg::CMAX + c] = __builtin_bit_cast(unsigned short, (_Float16)((v[c][e] - (float)h) * kSplitScale));
+            }
+        u32x2_t* const dh = reinterpret_cast<u32x2_t*>(sHi + pr * RS + pc * Cfg::CMAX);      // 416 pr + 24 (pc / 4) bytes
+        u32x2_t* const dl = reinterpret_cast<u32x2_t*>(sLo + pr * RS + pc * Cfg::CMAX);
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            dh[i] = u32x2_t{(unsigned)hh[4 * i] | ((unsigned)hh[4 * i + 1] << 16), (unsigned)hh[4 * i + 2] | ((unsigned)hh[4 * i + 3] << 16)};
+            dl[i] = u32x2_t{(unsigned)ll[4 * i] | ((unsigned)ll[4 * i + 1] << 16), (unsigned)ll[4 * i + 2] | ((unsigned)ll[4 * i + 3] << 16)};
         }
     }
     __syncthreads();
@@ -719,16 +744,14 @@ __global__ void __launch_bounds__(256) RT_WAVES_PER_EU(4) conv_s3_first_kernel(C
     const int oy = ty0 + wv, ox = tx0 + l31;
     const bool inb = oy < p.Ho && ox < p.Wo;
     const int cs32 = (int)p.y_cstride;
-    const int cb = nblk * 32;
     const buf_rsrc rs_y = make_buf(elem_ptr(p.y, (int64_t)n * p.y_bstride + p.y_off, 4));
     const int act = p.act;
     auto epilogue = [&](auto ACT) {
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            const f32x4 bv = *reinterpret_cast<const f32x4*>(p.bias + cb + 8 * q + 4 * kg);
             f32x4 o;
 #pragma unroll
-            for (int e = 0; e < 4; e++) o[e] = apply_act_fast(fmaf(acc_c[4 * q + e], kSplitInv, acc_m[4 * q + e]) + bv[e], decltype(ACT)::value);
+            for (int e = 0; e < 4; e++) o[e] = apply_act_fast(fmaf(acc_c[4 * q + e], kSplitInv, acc_m[4 * q + e]) + bv[q][e], decltype(ACT)::value);
             if constexpr (YIL) {
                 const unsigned vo = (inb && cb + 8 * q + 4 * kg < p.Cout) ? (unsigned)((oy * p.y_ystride + ox) * 4 + 4 * kg * cs32) * 4u : kBufOOB;
                 buf_store4(o, rs_y, vo, (unsigned)((cb + 8 * q) * cs32) * 4u);

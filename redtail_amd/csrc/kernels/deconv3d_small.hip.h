@@ -61,6 +61,28 @@ struct SmallTaps {
     static constexpr int NV = Z ? 27 : 9;
 };
 
+constexpr int kSmallU = 8;                 // channels whose loads the 2-D sparse path issues as one group (16: no faster, measured)
+
+// the value of `v` in the next lane of the wave; the last lane, which has none, keeps `last`
+__device__ static __forceinline__ float lane_right(float v, float last) {
+#ifdef HIPEMU
+    const float r = __shfl_down(v, 1);
+    return (threadIdx.x & 63) == 63 ? last : r;
+#else
+    // v_mov_b32_dpp wave_shl:1 -- lane l reads lane l + 1; lane 63 has no source and (bound_ctrl off) keeps the old value
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, last), __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
+#endif
+}
+// lane l's value of `v` (l wave-uniform), in every lane
+__device__ static __forceinline__ int lane_get(int v, int l) {
+#ifdef HIPEMU
+    return __shfl(v, l);
+#else
+    return __builtin_amdgcn_readlane(v, l);
+#endif
+}
+__device__ static __forceinline__ float lane_get(float v, int l) { return __builtin_bit_cast(float, lane_get(__builtin_bit_cast(int, v), l)); }
+
 // Z = false: the 2-D form (TensorRT addDeconvolution 3x3 stride 2, resnet18_2D_513x257_net.cpp:758-763): Dy = Dx = 1,
 // 2x2 output blocks, weights packed [K][COUT][phase 4][neighbour 4].
 template <int COUT, bool Z = true, typename TIN = float, typename TOUT = float>
@@ -106,7 +128,65 @@ __global__ void __launch_bounds__(256) deconv3d_s2_small_kernel(Deconv3dSmallArg
                         if (Taps::valid(f, j)) acc[co][f] = fmaf(xv[j], wk[co * Taps::NV + Taps::index(f, j)], acc[co][f]);
         }
     };
-    if (p.sparse == 1) contract_sparse(SmallTaps<Z, 0>{});                       // wave-uniform
+    // The 2-D form's last layer (deconv2D_3 of ResNet-18 2D: 32 -> 1 channel at full resolution) runs ~2 waves per SIMD, so nothing hides a
+    // load's latency but the wave's own loads, and what it pays for is the NUMBER of vector-memory instructions, whatever their lanes do.
+    // A loop of one channel per trip is a chain of K memory round trips of four loads each.  Here the loads of kSmallU channels are one
+    // group, the next group is requested before the current one is multiplied (two register sets), and a lane fetches its own column
+    // only: neighbour x + 1 is the lane to the right's own value, taken by a lane shift.  Lane 63 of a wave has no such lane: its 2 x
+    // kSmallU neighbour values of a group are ONE load (lane e < 2 kSmallU fetches channel e % kSmallU of row e / kSmallU at lane 63's
+    // x + 1) and reach lane 63 as wave-uniform values.  17 instead of 32 loads per 8 channels; the same fmaf per output in the same
+    // order as contract_sparse: the same bits.
+    auto contract_sparse_2d = [&]() {
+        using Taps = SmallTaps<false, 0>;
+        constexpr int U = kSmallU;
+        const int lane = threadIdx.x & 63;
+        const unsigned e0 = (unsigned)lane_get((int)voff[1], 63), e1 = (unsigned)lane_get((int)voff[3], 63);      // out of range stays so
+        const unsigned veoff = (lane < U ? e0 : (lane < 2 * U ? e1 : kBufOOB)) + (unsigned)(lane % U) * cstride;
+        auto load_group = [&](float (&xo)[U][2], float& xe, int k0) __attribute__((always_inline)) {
+#pragma unroll
+            for (int u = 0; u < U; u++)
+#pragma unroll
+                for (int jy = 0; jy < 2; jy++) xo[u][jy] = Io<TIN>::load(rs_x, voff[2 * jy], (unsigned)(k0 + u) * cstride);
+            xe = Io<TIN>::load(rs_x, veoff, (unsigned)k0 * cstride);
+        };
+        auto channel = [&](const float (&xo)[2], float xe, int u) __attribute__((always_inline)) {
+            const float xv[4] = {xo[0], lane_right(xo[0], lane_get(xe, u)), xo[1], lane_right(xo[1], lane_get(xe, U + u))};
+#pragma unroll
+            for (int co = 0; co < COUT; co++)
+#pragma unroll
+                for (int f = 0; f < 4; f++)
+#pragma unroll
+                    for (int j = 0; j < 4; j++)
+                        if (Taps::valid(f, j)) acc[co][f] = fmaf(xv[j], wk[co * Taps::NV + Taps::index(f, j)], acc[co][f]);
+            wk += COUT * Taps::NV;
+        };
+        auto group = [&](const float (&xo)[U][2], float xe) __attribute__((always_inline)) {
+#pragma unroll
+            for (int u = 0; u < U; u++) channel(xo[u], xe, u);
+        };
+        const int ng = p.K / U;                   // wave-uniform
+        float xo0[U][2], xo1[U][2], xe0, xe1;
+        if (ng > 0) load_group(xo0, xe0, 0);
+        for (int g = 0; g < ng; g += 2) {
+            if (g + 1 < ng) load_group(xo1, xe1, (g + 1) * U);
+            group(xo0, xe0);
+            if (g + 1 >= ng) break;
+            if (g + 2 < ng) load_group(xo0, xe0, (g + 2) * U);
+            group(xo1, xe1);
+        }
+        const int rem = p.K - ng * U;             // K % kSmallU channels, one at a time
+        if (rem > 0) {
+            const float xe = Io<TIN>::load(rs_x, lane % U < rem ? veoff : kBufOOB, (unsigned)(ng * U) * cstride);
+            for (int u = 0; u < rem; u++) {
+                float xo[2];
+#pragma unroll
+                for (int jy = 0; jy < 2; jy++) xo[jy] = Io<TIN>::load(rs_x, voff[2 * jy], (unsigned)(ng * U + u) * cstride);
+                channel(xo, xe, u);
+            }
+        }
+    };
+    if (!Z && p.sparse == 1) { if constexpr (!Z) contract_sparse_2d(); }         // wave-uniform
+    else if (p.sparse == 1) contract_sparse(SmallTaps<Z, 0>{});
     else if (Z && p.sparse == 1 + 4) contract_sparse(SmallTaps<Z, Z ? 4 : 0>{});    // depth axis with pad 0
     else {
         for (int k = 0; k < p.K; k++, wk += COUT * NJ * NJ) {
