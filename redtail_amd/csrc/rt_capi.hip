@@ -1100,14 +1100,32 @@ struct FoldFactor {
     std::map<rtStream, std::pair<void*, size_t>> own;      // the fallback blocks: one per stream the plan was enqueued on without a workspace
 };
 
+// Launch-time knobs of the environment (A/B and test switches; read_conv_knobs), with their defaults
+struct ConvKnobs {
+    int xcd = 1, trace = 0;       // RT_CONV_XCD, RT_CONV_TRACE
+    int rb_tiles = 0;             // RT_RB_TILES (experimental builds): the per-tile form of the fused residual block
+    int rbs_seg = 0;              // RT_RBS_SEG: rows per workgroup of the streaming residual block (0: chosen from the grid)
+    int ksplit = -1;              // RT_S3_KSPLIT: conv_s3_kernel's contraction groups (-1: chosen per CU, 0: none)
+    int s3p_grid = 0;             // RT_S3P_GRID: workgroups of the persistent kernel (test knob)
+    int zinner = 1;               // RT_Z_INNER: 3-D launches: depth slices fastest inside a tile (ConvArgs::z_inner); 0 = z outermost
+    int nbinner = 1;              // RT_NB_INNER: 3-D launches: blocks of 32 output channels fastest (ConvArgs::nb_inner); 0 = grid.y
+    int dw = -1;                  // RT_F16_DW: -1: where it applies (3x3x3 stride-1 Conv3D between interleaved fp16 tensors), 0: never
+    int dw_nseg = 0;              // RT_DW_NSEG: depth segments per tile pair (0: chosen from the grid)
+    int fold_u = 2;               // RT_FOLD_U: factored cost-volume fold: depth slices per trip of the combining pass (MI355X, NVSmall b8: 1: 0.84, 2: 0.68, 4: 1.07 ms)
+    int f16p_walk = -1;           // RT_F16P_WALK: transposed fp16 layers, four phases per workgroup: -1 walk down the class's depths (segments chosen), 0 one depth per workgroup, n > 0: n segments
+    int f16p_classes = 1;         // RT_F16P_CLASSES: ... 1: both depth classes (even / odd output depths) in one walk, 0: a launch per class
+    int small_walk = -1;          // RT_SMALL_IL_WALK: last transposed layer on interleaved fp16 input: 0 = one depth block per workgroup
+    int r4 = -1;                  // RT_F16_R4: -1: where it pays (3-D plans), 0: never, 1: every 3x3 stride-1 fp16 launch on interleaved tensors
+};
+
 struct rtConvPlan {
     std::vector<SubConv> subs;
     FoldFactor* ff = nullptr;
-    // launch-time knobs of the environment (A/B and test switches), read once at the plan's first enqueue: getenv walks the
-    // whole environment, and five look-ups per launch were a third of the host's time per launch
-    mutable std::once_flag env_once;   // the launch-time knobs below are read once per plan, by whichever context launches it first
+    // the knobs are read once per plan, at its first enqueue, by whichever context launches it first: getenv walks the whole
+    // environment, and five look-ups per launch were a third of the host's time per launch
+    mutable std::once_flag env_once;
+    mutable ConvKnobs opt;
     int softarg = 0;              // rt_conv_plan_set_softarg: 1 / 2 = the launch ends in a soft-argmax / soft-argmin over the output depth
-    mutable int opt_xcd = 1, opt_trace = 0, opt_rb_tiles = 0, opt_rbs_seg = 0, opt_s3p_grid = 0, opt_ksplit = -1, opt_r4 = -1, opt_zinner = 1, opt_nbinner = 1, opt_dw = -1, opt_dw_nseg = 0, opt_small_walk = -1, opt_fold_u = 2, opt_f16p_walk = -1, opt_f16p_classes = 1;
     float* bias_dev = nullptr;
     float* zeros_dev = nullptr;
     int act = 0, has_resid = 0, dtype = RT_F32;
@@ -1252,9 +1270,12 @@ int64_t pack_into(std::vector<float>& packed, const SubConv& sc, int cin_real, F
     return base;
 }
 
-int upload_weights(SubConv& sc, const std::vector<float>& packed) {
-    RT_HIP(hipMalloc((void**)&sc.w_dev, packed.size() * sizeof(float)));
-    RT_HIP(hipMemcpy(sc.w_dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
+// the launch's weight operands (fp32 slabs, or fp16 operands as uint16_t), in place of the ones it had
+template <typename T> int upload_weights(SubConv& sc, const std::vector<T>& packed) {
+    if (sc.w_dev) (void)hipFree(sc.w_dev);
+    sc.w_dev = nullptr;
+    RT_HIP(hipMalloc((void**)&sc.w_dev, packed.size() * sizeof(T)));
+    RT_HIP(hipMemcpy(sc.w_dev, packed.data(), packed.size() * sizeof(T), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -1342,6 +1363,16 @@ inline int exp_knob(const char* name, int dflt) { return env_int(name, dflt); }
 #else
 inline int exp_knob(const char*, int dflt) { return dflt; }
 #endif
+ConvKnobs read_conv_knobs() {
+    ConvKnobs k;
+    k.xcd = env_int("RT_CONV_XCD", k.xcd); k.trace = env_int("RT_CONV_TRACE", k.trace);
+    k.rb_tiles = exp_knob("RT_RB_TILES", k.rb_tiles); k.rbs_seg = env_int("RT_RBS_SEG", k.rbs_seg); k.ksplit = env_int("RT_S3_KSPLIT", k.ksplit);
+    k.s3p_grid = env_int("RT_S3P_GRID", k.s3p_grid); k.zinner = env_int("RT_Z_INNER", k.zinner); k.nbinner = env_int("RT_NB_INNER", k.nbinner);
+    k.dw = env_int("RT_F16_DW", k.dw); k.dw_nseg = env_int("RT_DW_NSEG", k.dw_nseg); k.fold_u = env_int("RT_FOLD_U", k.fold_u);
+    k.f16p_walk = env_int("RT_F16P_WALK", k.f16p_walk); k.f16p_classes = env_int("RT_F16P_CLASSES", k.f16p_classes);
+    k.small_walk = env_int("RT_SMALL_IL_WALK", k.small_walk); k.r4 = env_int("RT_F16_R4", k.r4);
+    return k;
+}
 // RT_CONV_EXACT_FP32 as an API option: set from the descriptor's flags for the duration of one *_plan_create call
 thread_local int tl_exact_fp32 = 0;
 int exact_fp32() { return tl_exact_fp32 || env_int("RT_CONV_EXACT_FP32", 0) != 0; }
@@ -1423,10 +1454,7 @@ int upload_s3p(SubConv& sc, int cin_real, F wfun) {
                 packed[(((((size_t)t * 2 + c) * 2 + 0) * 2 + kg) * 32 + co) * 8 + e] = hi;
                 packed[(((((size_t)t * 2 + c) * 2 + 1) * 2 + kg) * 32 + co) * 8 + e] = lo;
             }
-    if (sc.w_dev) (void)hipFree(sc.w_dev);
-    sc.w_dev = nullptr;
-    RT_HIP(hipMalloc((void**)&sc.w_dev, packed.size() * 2));
-    RT_HIP(hipMemcpy(sc.w_dev, packed.data(), packed.size() * 2, hipMemcpyHostToDevice));
+    if (int rc = upload_weights(sc, packed)) return rc;
     sc.s3p = 1; sc.split3 = 0; sc.wino = 0;
     sc.CinPad = 32; sc.CC = 16; sc.NBW = 1; sc.TXW = 1; sc.TY = sc.NW = 8;
     return 0;
@@ -1452,10 +1480,7 @@ int upload_s3first(SubConv& sc, int cin_real, F wfun) {
                     packed[blk + ((((size_t)r * 2 + 0) * 2 + h) * 32 + co % 32) * 8 + e] = hi;
                     packed[blk + ((((size_t)r * 2 + 1) * 2 + h) * 32 + co % 32) * 8 + e] = lo;
                 }
-    if (sc.w_dev) (void)hipFree(sc.w_dev);
-    sc.w_dev = nullptr;
-    RT_HIP(hipMalloc((void**)&sc.w_dev, packed.size() * 2));
-    RT_HIP(hipMemcpy(sc.w_dev, packed.data(), packed.size() * 2, hipMemcpyHostToDevice));
+    if (int rc = upload_weights(sc, packed)) return rc;
     sc.s3first = 1; sc.s3p = 0; sc.split3 = 0; sc.wino = 0;
     sc.NBW = 1; sc.TXW = 1; sc.TY = sc.NW = 4;
     return 0;
@@ -2101,8 +2126,8 @@ int enqueue_fold_factor(const rtConvPlan* plan, const void* x, void* y, int batc
     // the combining pass over x < W - 1, then the last column (edge term) -- see fold_combine_kernel
     const dim3 grid((unsigned)rt::cdiv(ff->W - 1, 256), (unsigned)ff->H, (unsigned)(batch * (ff->K / G)));
     const dim3 lgrid((unsigned)rt::cdiv((int64_t)ff->H * ff->D * (ff->K / G) * batch, 256), 1u, 1u);
-    const int U = plan->opt_fold_u;
-    if (plan->opt_trace) {
+    const int U = plan->opt.fold_u;
+    if (plan->opt.trace) {
         const char* T = sc.y_f16 ? "f16" : "f32";
         const int U1 = U == 4 ? 4 : (U == 2 ? 2 : 1);
         fprintf(stderr, "[rt] fold_t<%d> grid %u x %u x %u\n", G, tgrid.x, tgrid.y, tgrid.z);
@@ -2513,10 +2538,7 @@ int repack_f16mma(rtConvPlan* plan) {
         if (!sc.zs_host.empty())
             RT_HIP(hipMemcpy(sc.zs_dev, sc.zs_host.data(), sc.zs_host.size() * sizeof(rt::ZSlice), hipMemcpyHostToDevice));
     }
-    if (sc.w_dev) (void)hipFree(sc.w_dev);
-    sc.w_dev = nullptr;
-    RT_HIP(hipMalloc((void**)&sc.w_dev, packed.size() * 2));
-    RT_HIP(hipMemcpy(sc.w_dev, packed.data(), packed.size() * 2, hipMemcpyHostToDevice));
+    if (int rc = upload_weights(sc, packed)) return rc;
     if (sc.choff_dev) (void)hipFree(sc.choff_dev);
     sc.choff_dev = nullptr;
     const int ip = sc.x_pitch ? sc.x_pitch : plan->win;
@@ -2544,10 +2566,7 @@ int repack_f16first(rtConvPlan* plan) {
                     std::memcpy(&bits, &hv, 2);
                     packed[((((size_t)(co / 32) * 5 + r) * 2 + h) * 32 + co % 32) * 8 + e] = bits;
                 }
-    if (sc.w_dev) (void)hipFree(sc.w_dev);
-    sc.w_dev = nullptr;
-    RT_HIP(hipMalloc((void**)&sc.w_dev, packed.size() * 2));
-    RT_HIP(hipMemcpy(sc.w_dev, packed.data(), packed.size() * 2, hipMemcpyHostToDevice));
+    if (int rc = upload_weights(sc, packed)) return rc;
     sc.NBW = 1; sc.TXW = 1; sc.TY = sc.NW = 4;
     sc.wino = 0; sc.s3p = sc.split3 = sc.s3first = 0; sc.f16first = 1;
     return 0;
@@ -2590,11 +2609,8 @@ int repack_f32(rtConvPlan* plan) {
         if (!sc.zs_host.empty())
             RT_HIP(hipMemcpy(sc.zs_dev, sc.zs_host.data(), sc.zs_host.size() * sizeof(rt::ZSlice), hipMemcpyHostToDevice));
     }
-    if (!sc.s3p && !sc.s3first) {
-        if (sc.w_dev) (void)hipFree(sc.w_dev);
-        sc.w_dev = nullptr;
+    if (!sc.s3p && !sc.s3first)
         if (int rc = upload_weights(sc, packed)) return rc;
-    }
     if (sc.choff_dev) (void)hipFree(sc.choff_dev);
     sc.choff_dev = nullptr;
     const int ip = sc.x_pitch ? sc.x_pitch : plan->win;
@@ -2612,13 +2628,10 @@ int switch_conv3d_f16mma(rtConvPlan* plan, bool on) {
     const int cin_real = plan->c3d_cin, taps = sc.KH * sc.KW;
     const std::vector<float>& w = plan->w_canon;
     auto wfun = [&](int co, int ci, int u, int v) { return w[((size_t)co * cin_real + ci) * taps + u * sc.KW + v]; };
-    if (sc.w_dev) (void)hipFree(sc.w_dev);
-    sc.w_dev = nullptr;
     if (on) {
         std::vector<uint16_t> packed;
         pack_f16_into(packed, sc, cin_real, wfun);
-        RT_HIP(hipMalloc((void**)&sc.w_dev, packed.size() * 2));
-        RT_HIP(hipMemcpy(sc.w_dev, packed.data(), packed.size() * 2, hipMemcpyHostToDevice));
+        if (int rc = upload_weights(sc, packed)) return rc;
         sc.split3 = 0; sc.f16mma = 1;
     } else {
         sc.f16mma = 0; sc.split3 = 1;
@@ -3011,517 +3024,594 @@ extern "C" int rt_conv_enqueue_hint(const rtConvPlan* plan, const void* x, void*
 // from x2 (the right images, a separate binding: reference sample_app/main.cpp:290-300), y holds 2 * batch samples.  The towers share their
 // weights (resnet18_2D_513x257_net.cpp:48-64 / 320-336 read the same tensors), so this is the launch over [left | right] the executor's
 // siamese merge makes of every other tower layer.  Only the first-layer kernels have the form (5x5 stride 2 on <= 3 channels).
-namespace { thread_local const void* tl_twin_x2 = nullptr; thread_local int tl_twin_from = 0; }
 extern "C" int rt_conv_plan_supports_twin_input(const rtConvPlan* plan) {
     return plan && plan->subs.size() == 1 && (plan->subs[0].s3first || plan->subs[0].f16first) && !plan->has_resid && env_int("RT_NO_TWIN_INPUT", 0) == 0;
 }
+
+// ---- the launches of a plan: one launcher per kernel family, enqueue_conv walks the plan's sub-plans over them ------
+namespace {
+// What one rt_conv_enqueue* call hands to the launchers
+struct Launch {
+    const rtConvPlan* plan;
+    const void *x, *x2;        // x2: rt_conv_enqueue_twin_input (first layers only), samples x2_from .. batch - 1 are read from it; else null, 0
+    int x2_from;
+    void* y;
+    const void* residual;
+    int batch;
+    rtStream s;
+    int hints;
+};
+
+// f(std::true_type / std::false_type ...), one per flag: run-time flags pick a template instantiation (all 2^n are instantiated)
+template <typename F> void with_bools(F&& f) { f(); }
+template <typename F, typename... Rest> void with_bools(F&& f, bool b, Rest... rest) {
+    if (b) with_bools([&](auto... r) { f(std::true_type{}, r...); }, rest...);
+    else with_bools([&](auto... r) { f(std::false_type{}, r...); }, rest...);
+}
+
+// deconv3d_small.hip.h: stride-2 transposed 3x3x3 / 3x3 window with <= 2 output channels, its interleaved-input forms on the matrix cores
+int enqueue_small3d(const Launch& L, const SubConv& sc) {
+    const rtConvPlan* plan = L.plan;
+    const int batch = L.batch;
+    rt::Deconv3dSmallArgs a = sc.s3;
+    a.x = static_cast<const float*>(L.x); a.y = static_cast<float*>(L.y); a.w = sc.w_dev; a.bias = plan->bias_dev;
+    a.resid = plan->has_resid ? static_cast<const float*>(L.residual) : nullptr;
+    a.act = plan->act; a.x_bstride = plan->x_bstride; a.y_bstride = plan->y_bstride;
+    const int64_t gz = (int64_t)batch * a.Mz;
+    RT_REQUIRE(gz <= 65535 && (a.Hx + 1) / 2 <= 65535, "rt_conv_enqueue: grid limit exceeded");
+    dim3 grid((unsigned)rt::cdiv((a.Wx + 1) / 2, 256), (unsigned)((a.Hx + 1) / 2), (unsigned)gz);
+    // deconv3d_s2_small_kernel<C, second template argument, TIN, TOUT> -- the branches below, in their order
+    if (plan->opt.trace && !(sc.small3d == 1 && sc.x_il8))
+        fprintf(stderr, "[rt] deconv3d_s2_small<%d,%d,%s,%s> grid %u x %u x %u\n", a.C == 1 ? 1 : 2, sc.small3d == 1 ? 1 : 0,
+                sc.x_f16 ? "f16" : "f32", (sc.small3d == 2 && sc.x_f16 && sc.y_f16) ? "f16" : "f32", grid.x, grid.y, grid.z);
+    if (sc.small3d == 2 && sc.x_f16) {          // half2 mode: fp16 activations in, fp32 (binding) or fp16 out
+        if (sc.y_f16) {
+            if (a.C == 1) hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<1, false, _Float16, _Float16>), grid, dim3(256), 0, S(L.s), a);
+            else hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<2, false, _Float16, _Float16>), grid, dim3(256), 0, S(L.s), a);
+        } else {
+            if (a.C == 1) hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<1, false, _Float16, float>), grid, dim3(256), 0, S(L.s), a);
+            else hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<2, false, _Float16, float>), grid, dim3(256), 0, S(L.s), a);
+        }
+    } else if (sc.small3d == 1 && sc.x_f16 && sc.x_il8) {     // ... with a channel-interleaved (K/8, D, H, W, 8) input: on the matrix cores
+        a.w = static_cast<const float*>(sc.small_il_dev);
+        const int groups = (int)rt::cdiv((a.Wx + 1) / 2, 16);
+        RT_REQUIRE(batch <= 65535, "rt_conv_enqueue: grid limit exceeded");
+        const int rowpairs = (int)rt::cdiv((a.Hx + 1) / 2, 2);
+        if (plan->softarg) {
+            // the walk is the soft-argmax's reduction axis: one segment, y = the (batch, 1, Hx, Wx) map
+            RT_REQUIRE(a.K == 32 && a.C == 1 && !a.resid && rowpairs <= 65535, "rt_conv_enqueue: plan lost the form its fused soft-argmax needs");
+            a.y_bstride = (int64_t)a.Hx * a.Wx;
+            dim3 gw((unsigned)rt::cdiv(groups, 4), (unsigned)rowpairs, (unsigned)batch);
+            if (plan->opt.trace) fprintf(stderr, "[rt] deconv3d_s2_ilw<%d> grid %u x %u x %u segments 1 x %d\n", plan->softarg == 2 ? 2 : 1, gw.x, gw.y, gw.z, a.Mz);
+            if (plan->softarg == 2) hipLaunchKernelGGL(rt::deconv3d_s2_ilw_kernel<2>, gw, dim3(256), 0, S(L.s), a, a.Mz, 1);
+            else hipLaunchKernelGGL(rt::deconv3d_s2_ilw_kernel<1>, gw, dim3(256), 0, S(L.s), a, a.Mz, 1);
+        } else if (a.K == 32 && plan->opt.small_walk != 0) {
+            // the depth walk (deconv3d_s2_ilw_kernel): segments long enough to pay for their prologue (>= 8 depth blocks), as many as
+            // it takes to give every SIMD about two waves
+            const int64_t waves = (int64_t)groups * rowpairs * batch;
+            int nseg = (int)std::min<int64_t>(std::max<int64_t>(1, rt::cdiv((int64_t)8 * device_cus(), waves)), std::max(1, a.Mz / 8));
+            const int seg_len = (int)rt::cdiv(a.Mz, nseg);
+            nseg = (int)rt::cdiv(a.Mz, seg_len);
+            RT_REQUIRE(rowpairs <= 65535, "rt_conv_enqueue: grid limit exceeded");
+            dim3 gw((unsigned)(rt::cdiv(groups, 4) * nseg), (unsigned)rowpairs, (unsigned)batch);
+            if (plan->opt.trace) fprintf(stderr, "[rt] deconv3d_s2_ilw<0> grid %u x %u x %u segments %d x %d\n", gw.x, gw.y, gw.z, nseg, seg_len);
+            hipLaunchKernelGGL(rt::deconv3d_s2_ilw_kernel<0>, gw, dim3(256), 0, S(L.s), a, seg_len, nseg);
+        } else {
+            dim3 g2((unsigned)(rt::cdiv(groups, 4 * rt::kSmallIlIters) * a.Mz), (unsigned)rowpairs, (unsigned)batch);
+            if (plan->opt.trace) fprintf(stderr, "[rt] deconv3d_s2_il grid %u x %u x %u\n", g2.x, g2.y, g2.z);
+            hipLaunchKernelGGL(rt::deconv3d_s2_il_kernel, g2, dim3(256), 0, S(L.s), a);
+        }
+    } else if (sc.small3d == 1 && !sc.x_f16 && sc.x_il8) {    // fp32 engines: (K/4, D, H, W, 4) in, split form on the matrix cores
+        RT_REQUIRE(sc.small_il_dev && sc.small_il_f32, "rt_conv_enqueue: interleaved fp32 input without its weight operands (rt_conv_plan_set_layouts)");
+        a.w = static_cast<const float*>(sc.small_il_dev);
+        const int groups = (int)rt::cdiv((a.Wx + 1) / 2, 16);
+        RT_REQUIRE(batch <= 65535, "rt_conv_enqueue: grid limit exceeded");
+        dim3 g2((unsigned)(rt::cdiv(groups, 4 * rt::kSmallIlIters) * a.Mz), (unsigned)rt::cdiv((a.Hx + 1) / 2, 2), (unsigned)batch);
+        if (plan->opt.trace) fprintf(stderr, "[rt] deconv3d_s2_il4 grid %u x %u x %u\n", g2.x, g2.y, g2.z);
+        hipLaunchKernelGGL(rt::deconv3d_s2_il4_kernel, g2, dim3(256), 0, S(L.s), a);
+    } else if (sc.small3d == 1 && sc.x_f16) {   // 3-D last layer in half2 mode: fp16 (K,D,H,W) in, fp32 volume out
+        if (a.C == 1) hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<1, true, _Float16, float>), grid, dim3(256), 0, S(L.s), a);
+        else hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<2, true, _Float16, float>), grid, dim3(256), 0, S(L.s), a);
+    } else if (sc.small3d == 2) {
+        if (a.C == 1) hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<1, false>), grid, dim3(256), 0, S(L.s), a);
+        else hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<2, false>), grid, dim3(256), 0, S(L.s), a);
+    } else {
+        if (a.C == 1) hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<1, true>), grid, dim3(256), 0, S(L.s), a);
+        else hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<2, true>), grid, dim3(256), 0, S(L.s), a);
+    }
+    RT_LAUNCH_CHECK("deconv3d_s2_small_kernel");
+    return 0;
+}
+
+// The kernel arguments every other family starts from: the 4 x 32 * TXW-tiled launch of one sub-plan
+rt::ConvArgs conv_args(const Launch& L, const SubConv& sc) {
+    const rtConvPlan* plan = L.plan;
+    rt::ConvArgs a;
+    a.z_inner = 0; a.nb_inner = 0;
+    a.x = static_cast<const float*>(L.x);
+    a.x2 = static_cast<const float*>(L.x2); a.x2_from = L.x2_from;
+    a.y = static_cast<float*>(L.y);
+    a.w = sc.w_dev;
+    a.bias = plan->bias_dev;
+    a.zeros = plan->zeros_dev;
+    a.dbg = nullptr;
+#ifdef RT_KERNEL_TIMING
+    if (const char* e = getenv("RT_DBG_PTR")) a.dbg = (unsigned long long*)strtoull(e, nullptr, 0);
+#endif
+    a.resid = plan->has_resid ? static_cast<const float*>(L.residual) : nullptr;
+    a.ch_off = sc.choff_dev;
+    a.ch_shift = sc.shift_dev;
+    a.w_exact = plan->w_f16;
+    a.zs = sc.zs_dev;
+    a.CinPad = sc.CinPad; a.Cout = sc.Cout;
+    a.Hi = sc.Hi; a.Wi = sc.Wi; a.Ho = sc.Ho; a.Wo = sc.Wo;
+    a.x_pitch = sc.x_pitch ? sc.x_pitch : sc.Wi;
+    a.pad_y = sc.pad_y; a.pad_x = sc.pad_x; a.nz = sc.nz;
+    a.tiles_x = (int)rt::cdiv(sc.Wo, 32 * sc.TXW);
+    a.act = plan->act;
+    a.xcd_order = plan->opt.xcd;
+    a.x_bstride = plan->x_bstride; a.y_bstride = plan->y_bstride;
+    a.y_cstride = sc.y_cstride; a.y_zstride = sc.y_zstride; a.y_off = sc.y_off;
+    // Conv3D writing a channel-major interleaved tensor (K/8, D, H, W, 8): a depth slice is 8 * H * W elements apart
+    if (plan->is_conv3d && !plan->c3d_dchw && sc.y_il8) a.y_zstride = 8 * sc.y_zstride;
+    a.y_ystride = sc.y_ystride; a.y_xstride = sc.y_xstride;
+    a.r_cstride = sc.r_cstride ? sc.r_cstride : sc.y_cstride;
+    a.r_bstride = plan->r_bstride ? plan->r_bstride : plan->y_bstride;
+    a.r_il8 = sc.r_il8;
+    a.batch = L.batch; a.cin_real = sc.cin_real; a.x_cstride = (int64_t)sc.Hi * a.x_pitch;
+    return a;
+}
+
+// deconv_s3p.hip.h: fp32 tensors, four phases per workgroup in split-fp16 form, planar input and output
+int enqueue_deconv_s3p(const Launch& L, const SubConv& sc, rt::ConvArgs& a) {
+    a.tiles_x = (int)rt::cdiv(sc.Wi, 32);
+    const int tiles = a.tiles_x * (int)rt::cdiv(sc.Hi, 4), nblk = (int)rt::cdiv(sc.Cout, 32);
+    RT_REQUIRE(!sc.x_il8 && !sc.x_f16 && !sc.y_f16, "rt_conv_enqueue: the fp32 four-phase transposed kernel takes a planar fp32 input and writes fp32");
+    RT_REQUIRE((int64_t)L.batch * sc.nz <= 65535, "rt_conv_enqueue: grid limit exceeded");
+    RT_REQUIRE(sc.y_cstride * (int64_t)sc.Cout < (1ll << 29), "rt_conv_enqueue: output sample exceeds 2 GB (32-bit buffer offsets)");
+    dim3 g((unsigned)tiles, (unsigned)nblk, (unsigned)(L.batch * sc.nz));
+    if (L.plan->opt.trace) fprintf(stderr, "[rt] deconv_s3p<%d> r%d grid %u x %u x %u\n", sc.y_il8 ? 1 : 0, sc.r_il8, g.x, g.y, g.z);
+    if (sc.y_il8) hipLaunchKernelGGL(rt::deconv_s3p_kernel<true>, g, dim3(256), 0, S(L.s), a);
+    else hipLaunchKernelGGL(rt::deconv_s3p_kernel<false>, g, dim3(256), 0, S(L.s), a);
+    RT_LAUNCH_CHECK("deconv_s3p_kernel");
+    return 0;
+}
+
+// deconv_f16p.hip.h: transposed 3-D convolution between interleaved fp16 tensors, four phases per workgroup: tiles of the INPUT grid, one z
+// per output depth.  took_next: the launch covered the plan's next sub-plan as well (both depth classes in one walk)
+int enqueue_deconv_f16p(const Launch& L, const SubConv& sc, rt::ConvArgs& a, bool& took_next) {
+    const rtConvPlan* plan = L.plan;
+    const int batch = L.batch;
+    a.tiles_x = (int)rt::cdiv(sc.Wi, 32);
+    const int tiles = a.tiles_x * (int)rt::cdiv(sc.Hi, 4), nblk = (int)rt::cdiv(sc.Cout, 32);
+    RT_REQUIRE(sc.x_il8 && sc.y_il8 && sc.x_f16 && sc.y_f16, "rt_conv_enqueue: the four-phase transposed kernel takes interleaved fp16 tensors");
+    a.z_inner = plan->opt.zinner != 0 ? 1 : 0;
+    RT_REQUIRE(batch <= 65535 && (int64_t)batch * sc.nz <= 65535, "rt_conv_enqueue: grid limit exceeded");
+    dim3 g = a.z_inner ? dim3((unsigned)(tiles * sc.nz), (unsigned)nblk, (unsigned)batch) : dim3((unsigned)tiles, (unsigned)nblk, (unsigned)(batch * sc.nz));
+    if (plan->opt.f16p_walk != 0 && (!plan->has_resid || sc.r_il8)) {       // (a planar skip tensor -- not what the executor uses -- stays with the per-depth kernel)
+        // the walk (deconv_f16pw_kernel): a workgroup keeps its tile and takes a segment of the class's output depths.  Segments as
+        // long as the grid allows: cost = rounds over the chip's 3 workgroups per CU x (slices per segment + one slice's worth of
+        // fill and drain)
+        // Both depth classes in ONE walk (slice m of the even class, then slice m of the odd one: their input slices are the same and
+        // the next): the second sub-plan rides along when it is the same launch in everything but weights, slices and gather table
+        rt::DeconvWalkB wb{};
+        const SubConv* sb = (&sc == &plan->subs[0] && plan->subs.size() == 2) ? &plan->subs[1] : nullptr;
+        if (sb && plan->opt.f16p_classes != 0 && sb->dp4 && sb->f16mma && sb->x_il8 && sb->y_il8 && sb->x_f16 && sb->y_f16 && sb->r_il8 == sc.r_il8 &&
+            sb->Hi == sc.Hi && sb->Wi == sc.Wi && sb->Ho == sc.Ho && sb->Wo == sc.Wo && sb->Cout == sc.Cout && sb->x_pitch == sc.x_pitch &&
+            sb->y_cstride == sc.y_cstride && sb->y_ystride == sc.y_ystride && sb->r_cstride == sc.r_cstride) {
+            wb.w = static_cast<const float*>(sb->w_dev); wb.zs = sb->zs_dev; wb.ch_off = sb->choff_dev; wb.CinPad = sb->CinPad; wb.nz = sb->nz;
+            took_next = true;
+        }
+        const int nzw = std::max(sc.nz, wb.zs ? wb.nz : 0);                             // slice indices of the walk
+        const double per_m = wb.zs ? (double)(sc.CinPad + wb.CinPad) / sc.CinPad : 1.0; // work per slice index, in slices of this class
+        const int64_t slots = (int64_t)3 * device_cus(), base = (int64_t)tiles * nblk * batch;
+        // (among segmentations within 5 % of the cheapest, the one with the most segments: rounds of long walks do not stay in step and
+        //  their tail is a whole walk long -- NVSmall deconv3D_2 at batch 8: 1 segment 1.31 ms, 4 segments 1.26, both "cost" 146-152)
+        int nseg = 1;
+        double best = 1e30;
+        auto seg_cost = [&](int ns) {
+            const int seg = (int)rt::cdiv(nzw, ns);
+            return (int)rt::cdiv(nzw, seg) != ns ? 1e30 : (double)rt::cdiv(base * ns, slots) * (seg * per_m + 1.0);
+        };
+        for (int ns = 1; ns <= nzw; ns++) best = std::min(best, seg_cost(ns));
+        for (int ns = 1; ns <= nzw; ns++)
+            if (seg_cost(ns) <= 1.05 * best) nseg = ns;
+        if (plan->opt.f16p_walk > 0) nseg = std::min(plan->opt.f16p_walk, nzw);            // (RT_F16P_WALK=<n>: n segments)
+        a.dw_seg = (int)rt::cdiv(nzw, nseg); a.dw_nseg = nzw; a.dw_cpc = sc.nz; a.nz = (int)rt::cdiv(nzw, a.dw_seg);
+        RT_REQUIRE((int64_t)batch * a.nz <= 65535, "rt_conv_enqueue: grid limit exceeded");
+        dim3 gw = a.z_inner ? dim3((unsigned)(tiles * a.nz), (unsigned)nblk, (unsigned)batch) : dim3((unsigned)tiles, (unsigned)nblk, (unsigned)(batch * a.nz));
+        if (plan->opt.trace) fprintf(stderr, "[rt] deconv_f16pw grid %u x %u x %u, %d slice indices per segment, %d class(es)\n", gw.x, gw.y, gw.z, a.dw_seg, wb.zs ? 2 : 1);
+        hipLaunchKernelGGL(rt::deconv_f16pw_kernel, gw, dim3(256), 0, S(L.s), a, wb);
+        RT_LAUNCH_CHECK("deconv_f16pw_kernel");
+        return 0;
+    }
+    if (plan->opt.trace) fprintf(stderr, "[rt] deconv_f16p grid %u x %u x %u\n", g.x, g.y, g.z);
+    hipLaunchKernelGGL(rt::deconv_f16p_kernel, g, dim3(256), 0, S(L.s), a);
+    RT_LAUNCH_CHECK("deconv_f16p_kernel");
+    return 0;
+}
+
+// The grid of a tiled launch -- (tiles of the output plane, blocks of 32 * NBW output channels, batch * z-slices) -- and what 3-D plans
+// fold of it into grid.x (conv_mfma.hip.h: ConvArgs::z_inner, ::nb_inner)
+struct ConvGrid {
+    dim3 grid;
+    int64_t gz = 0;                     // batch * z-slices
+    unsigned nz_fold = 0, batch = 0;    // nz_fold: the z-slices folded into grid.x, z fastest (0: they stay in grid.z)
+    int tiles_y = 0, nb_fold = 0;       // nb_fold: the blocks of output channels folded in as well, fastest of all (0: they stay in grid.y)
+    dim3 fold(dim3 g) const {
+        if (nz_fold) g = dim3(g.x * nz_fold, g.y, batch);
+        return nb_fold ? dim3(g.x * g.y, 1u, g.z) : g;
+    }
+};
+
+// ... for the sub-plan's own tile; sets a.z_inner and a.nb_inner to match
+int conv_grid(const Launch& L, const SubConv& sc, rt::ConvArgs& a, ConvGrid& g) {
+    const rtConvPlan* plan = L.plan;
+    g.tiles_y = (int)rt::cdiv(sc.Ho, sc.TY);
+    g.gz = (int64_t)L.batch * sc.nz;
+    g.batch = (unsigned)L.batch;
+    // split-fp16 / fp16-operand launches of 3-D plans fold the z-slices into grid.x, z fastest (conv_mfma.hip.h: ConvArgs::z_inner)
+    // (fp16-operand launches on interleaved tensors only: measured on ResNet-18 3D fp32 the planar split kernel is 3 % SLOWER with z fastest,
+    //  8.56 vs 8.27 ms per pair -- RT_Z_INNER=2 folds those too)
+    const bool zin = sc.nz > 1 && plan->opt.zinner != 0 && (sc.f16mma || (sc.split3 && plan->opt.zinner == 2)) &&
+                     (int64_t)rt::cdiv(sc.Wo, 32 * sc.TXW) * rt::cdiv(sc.Ho, sc.TY) * sc.nz < (1ll << 30);
+    a.z_inner = zin ? 1 : 0;
+    g.nz_fold = zin ? (unsigned)sc.nz : 0u;
+    RT_REQUIRE(zin ? L.batch <= 65535 : g.gz <= 65535, "rt_conv_enqueue: batch * depth = %lld exceeds the grid limit", (long long)g.gz);
+    RT_REQUIRE(sc.y_cstride * (int64_t)sc.Cout < (1ll << 29), "rt_conv_enqueue: output sample exceeds 2 GB (32-bit buffer offsets)");
+    g.grid = dim3((unsigned)(a.tiles_x * g.tiles_y), (unsigned)rt::cdiv(sc.Cout, 32 * sc.NBW), (unsigned)g.gz);
+    // ... and 3-D launches with several blocks of 32 output channels fold those in as well, fastest of all (ConvArgs::nb_inner); the direct
+    // and the persistent kernel take the plain grid
+    if (!sc.direct && !sc.s3p && !plan->is2d && g.grid.y > 1 && plan->opt.nbinner != 0 && (sc.f16mma || sc.split3) && !sc.rb && sc.NBW == 1 &&
+        (int64_t)g.grid.x * g.grid.y * (zin ? sc.nz : 1) < (1ll << 30))
+        g.nb_fold = (int)g.grid.y;
+    a.nb_inner = g.nb_fold;
+    return 0;
+}
+
+// conv_direct_f32_kernel (conv_mfma.hip.h): <= 2 output channels on the vector ALU
+int enqueue_direct(const Launch& L, const SubConv& sc, const rt::ConvArgs& a, const ConvGrid& g) {
+    RT_REQUIRE(sc.Ho <= 65535, "rt_conv_enqueue: output too tall for the direct kernel");
+    dim3 dgrid((unsigned)rt::cdiv(sc.Wo, 256), (unsigned)sc.Ho, (unsigned)g.gz);
+    bool launched = false;
+#define RT_DIRECT(co, kh, kw)                                                                                         \
+    if (!launched && sc.Cout <= co && sc.KH == kh && sc.KW == kw) {                                                   \
+        hipLaunchKernelGGL((rt::conv_direct_f32_kernel<co, kh, kw>), dgrid, dim3(256), 0, S(L.s), a, sc.S, sc.cin_real); \
+        launched = true;                                                                                              \
+    }
+    RT_DIRECT(1, 1, 1) RT_DIRECT(1, 1, 2) RT_DIRECT(1, 2, 1) RT_DIRECT(1, 2, 2) RT_DIRECT(1, 3, 3) RT_DIRECT(1, 5, 5)
+    RT_DIRECT(2, 1, 1) RT_DIRECT(2, 1, 2) RT_DIRECT(2, 2, 1) RT_DIRECT(2, 2, 2) RT_DIRECT(2, 3, 3) RT_DIRECT(2, 5, 5)
+#undef RT_DIRECT
+    if (!launched) return fail(RT_E_UNSUPPORTED, "conv (direct): window %dx%d not instantiated", sc.KH, sc.KW);
+    RT_LAUNCH_CHECK("conv_direct_f32_kernel");
+    return 0;
+}
+
+#ifdef RT_EXPERIMENTAL
+// conv_s3p_kernel (conv_split.hip.h): persistent, one 8-wave workgroup per CU walks a contiguous range of tiles (RT_S3P_GRID: test knob)
+int enqueue_s3p(const Launch& L, const SubConv& sc, const rt::ConvArgs& a, const ConvGrid& g) {
+    const rtConvPlan* plan = L.plan;
+    const int64_t T = (int64_t)a.tiles_x * g.tiles_y * L.batch;
+    int64_t n = std::min<int64_t>(T, (plan->opt.s3p_grid > 0 ? plan->opt.s3p_grid : device_cus()));
+    if (n >= 8) n -= n % 8;
+    dim3 pgrid((unsigned)std::max<int64_t>(n, 1));
+    if (plan->opt.trace)
+        fprintf(stderr, "[rt] conv_s3p x%d y%d r%d tiles %lld grid %u\n", sc.x_il8, sc.y_il8, sc.r_il8, (long long)T, pgrid.x);
+    with_bools([&](auto xi, auto yi) { hipLaunchKernelGGL((rt::conv_s3p_kernel<8, xi, yi>), pgrid, dim3(512), 0, S(L.s), a); }, sc.x_il8, sc.y_il8);
+    RT_LAUNCH_CHECK("conv_s3p_kernel");
+    return 0;
+}
+#endif
+
+// The fused residual block: the streaming forms (conv_rbs.hip.h, conv_rbd.hip.h, conv_rbh.hip.h) and the experimental per-tile form
+int enqueue_resblock(const Launch& L, const SubConv& sc, const rt::ConvArgs& a, const ConvGrid& g) {
+    const rtConvPlan* plan = L.plan;
+    rt::RBArgs ra;
+    ra.c = a;
+    ra.c.resid = static_cast<const float*>(L.x);          // the block's input is its skip connection
+    ra.c.r_cstride = a.x_cstride; ra.c.r_bstride = plan->x_bstride; ra.c.r_il8 = sc.x_il8;
+    ra.w1 = plan->rb_w1_dev; ra.bias1 = plan->rb_bias1_dev; ra.act1 = plan->rb_act1; ra.cmid = plan->rb_cmid; ra.seg = 0;
+    // 32 -> 32 -> 32 channels, ELU after both, on interleaved tensors (the feature towers): the streaming form, strips of 30 columns x
+    // segments of 16 rows (conv_rbs.hip.h); everything else: one 4 x 32 tile per workgroup
+    if (sc.x_il8 && sc.y_il8 && plan->cin == 32 && plan->rb_cmid == 32 && sc.Cout == 32 && plan->rb_act1 == 1 && plan->act == 1 &&
+        plan->opt.rb_tiles == 0) {
+        ra.c.tiles_x = (int)rt::cdiv(sc.Wo, rt::S3RBSCfg::SW);
+        // rows per workgroup: the pipeline's fill and drain steps and the prologue are paid per segment, so longer segments
+        // cost fewer CU-cycles per row; shorter ones fill more CUs of an otherwise idle GPU (RT_RBS_SEG, default: see DESIGN.md 4.4)
+        // Measured in the running network (ResNet-18 2D, 1257x369, four contexts): 16 rows 2129, 24: 2178, 32: 2185, 48: 2067,
+        // 64: 1957 pairs/s (two launches of the layer-by-layer kernels: 2057); alone 16 rows are fastest (24.5 vs 32.4 us).
+        // Round 3, siamese batch-2 launches, six one-stream contexts: 32 rows 2315, 48: 2432, 64: 2457-2539, 96: 2441, 128: 2305 pairs/s;
+        // one context, synchronous execute(): 32 rows 0.60 ms per pair, 64: 0.74-0.76 ms.  So: throughput hint -> 64 rows while
+        // that leaves >= 120 workgroups; otherwise 32 rows while that leaves >= 120; otherwise 16.
+        int seg = plan->opt.rbs_seg;
+        const auto wgs = [&](int rows) { return ra.c.tiles_x * (int)rt::cdiv(sc.Ho, rows) * L.batch; };
+        if (seg <= 0) seg = ((L.hints & RT_HINT_THROUGHPUT) && wgs(64) >= 120) ? 64 : (wgs(32) >= 120 ? 32 : rt::S3RBSCfg::SEG);
+        seg = seg < 4 ? 4 : (seg > 240 ? 240 : (seg + 3) / 4 * 4);
+        ra.seg = seg;
+        dim3 sgrid((unsigned)(ra.c.tiles_x * (int)rt::cdiv(sc.Ho, seg)), 1u, (unsigned)L.batch);
+        if (plan->opt.trace) {
+            if (sc.x_f16) fprintf(stderr, "[rt] conv_f16rbd grid %u x %u x %u seg %d\n", sgrid.x, sgrid.y, sgrid.z, seg);
+            else fprintf(stderr, "[rt] conv_s3rb%c<%d> grid %u x %u x %u seg %d\n", plan->x_split ? 'd' : 's', plan->y_split ? 1 : 0, sgrid.x,
+                         sgrid.y, sgrid.z, seg);
+        }
+        if (sc.x_f16) {                         // half2 mode: fp16 tensors, fp16 operands
+            ra.w1 = plan->rbh_w1_dev; ra.c.w = plan->rbh_w2_dev;
+            hipLaunchKernelGGL(rt::conv_f16rbd_kernel, sgrid, dim3(512), 0, S(L.s), ra);
+            RT_LAUNCH_CHECK("conv_f16rbd_kernel");
+        } else if (plan->x_split) {             // pre-split input: the DMA-fed block (its own row order of the weight slabs)
+            ra.w1 = plan->rbd_w1_dev; ra.c.w = plan->rbd_w2_dev;
+            if (plan->y_split) hipLaunchKernelGGL(rt::conv_s3rbd_kernel<true>, sgrid, dim3(512), 0, S(L.s), ra);
+            else hipLaunchKernelGGL(rt::conv_s3rbd_kernel<false>, sgrid, dim3(512), 0, S(L.s), ra);
+            RT_LAUNCH_CHECK("conv_s3rbd_kernel");
+        } else {
+            if (plan->y_split) hipLaunchKernelGGL(rt::conv_s3rbs_kernel<true>, sgrid, dim3(512), 0, S(L.s), ra);
+            else hipLaunchKernelGGL(rt::conv_s3rbs_kernel<false>, sgrid, dim3(512), 0, S(L.s), ra);      // ELU / ELU, as in every tower block
+            RT_LAUNCH_CHECK("conv_s3rbs_kernel");
+        }
+        return 0;
+    }
+    if (sc.x_f16 || sc.y_f16)
+        return fail(RT_E_UNSUPPORTED, "rt_conv_enqueue: the half2 form of the residual block takes channel-interleaved fp16 tensors only (rt_conv_plan_set_layouts(1, 1, 1))");
+#ifdef RT_EXPERIMENTAL
+    dim3 rgrid((unsigned)(a.tiles_x * g.tiles_y), 1u, (unsigned)L.batch);
+    if (plan->opt.trace) fprintf(stderr, "[rt] conv_s3rb x%d y%d grid %u x %u\n", sc.x_il8, sc.y_il8, rgrid.x, rgrid.z);
+    with_bools([&](auto xi, auto yi) { hipLaunchKernelGGL((rt::conv_s3rb_kernel<xi, yi>), rgrid, dim3(256), 0, S(L.s), ra); }, sc.x_il8, sc.y_il8);
+    RT_LAUNCH_CHECK("conv_s3rb_kernel");
+    return 0;
+#else
+    return fail(RT_E_UNSUPPORTED, "rt_conv_enqueue: this build plans residual blocks for the streaming kernel only (32 -> 32 -> 32 channels, "
+                                   "ELU / ELU, interleaved tensors); the per-tile form is compiled with RT_EXPERIMENTAL");
+#endif
+}
+
+// conv_s3_first_kernel (conv_split.hip.h): 5x5 stride-2 first layer on <= 3 channels, split fp16
+int enqueue_s3first(const Launch& L, const SubConv& sc, const rt::ConvArgs& a, const ConvGrid& g) {
+    if (L.plan->opt.trace) fprintf(stderr, "[rt] conv_s3_first<%d> grid %u x %u x %u twin %d\n", sc.y_il8 ? 1 : 0, g.grid.x, g.grid.y, g.grid.z, a.x2 ? 1 : 0);
+    if (sc.y_il8) hipLaunchKernelGGL((rt::conv_s3_first_kernel<true>), g.grid, dim3(256), 0, S(L.s), a);
+    else hipLaunchKernelGGL((rt::conv_s3_first_kernel<false>), g.grid, dim3(256), 0, S(L.s), a);
+    RT_LAUNCH_CHECK("conv_s3_first_kernel");
+    return 0;
+}
+
+// ... and conv_f16_first_kernel: the same layer on fp16 operands, fp32 image -> fp16 tensor
+int enqueue_f16first(const Launch& L, const SubConv& sc, const rt::ConvArgs& a, const ConvGrid& g) {
+    if (L.plan->opt.trace) fprintf(stderr, "[rt] conv_f16_first<%d> grid %u x %u x %u twin %d\n", sc.y_il8 ? 1 : 0, g.grid.x, g.grid.y, g.grid.z, a.x2 ? 1 : 0);
+    if (sc.y_il8) hipLaunchKernelGGL((rt::conv_f16_first_kernel<true>), g.grid, dim3(256), 0, S(L.s), a, L.plan->cin);
+    else hipLaunchKernelGGL((rt::conv_f16_first_kernel<false>), g.grid, dim3(256), 0, S(L.s), a, L.plan->cin);
+    RT_LAUNCH_CHECK("conv_f16_first_kernel");
+    return 0;
+}
+
+// conv_s3_kernel (conv_split.hip.h): fp32 (or fp16-storage) tensors, 3-term fp16 split on the fp16 matrix pipe
+int enqueue_split3(const Launch& L, const SubConv& sc, const rt::ConvArgs& a, const ConvGrid& g) {
+    const rtConvPlan* plan = L.plan;
+    const dim3 grid = g.fold(g.grid);
+    const int trace = plan->opt.trace;
+    bool launched = false;
+    // split-K for launches that leave SIMDs with a single wave (the low-resolution layers; conv_split.hip.h): KS groups of
+    // 4 waves per workgroup, as many as the CU's 16 wave slots at this kernel's register budget allow.  Chosen from the
+    // per-sample grid so that a sample's result does not depend on the batch it travels in.
+    int ks = 1;
+    const int64_t per_cu = rt::cdiv((int64_t)g.grid.x * g.grid.y * (g.gz / L.batch), (int64_t)device_cus());
+    // Not with the throughput hint: there other contexts' launches fill the SIMDs, and a 16-wave workgroup with 139 KB of LDS
+    // keeps them off its CU (six one-stream contexts: 2502 against 2589 pairs/s; one context, synchronous: 0.541 against 0.557 ms).
+    if (plan->opt.ksplit > 0 || (plan->opt.ksplit < 0 && !(L.hints & RT_HINT_THROUGHPUT))) {
+        const int nch = a.CinPad / 16;
+        ks = plan->opt.ksplit > 0 ? plan->opt.ksplit : (per_cu == 1 && nch >= 4 ? 4 : (per_cu <= 2 && nch >= 2 ? 2 : 1));
+    }
+    if (sc.x_f16 || sc.y_f16) {                 // fp16 storage (3-D tensors of half2 mode): planar, 4-row tiles
+        // (the residual's layout is a run-time flag of the kernel: r_il8; an interleaved fp16 OUTPUT exists for fp32 planar input)
+        if (!sc.x_f16 && sc.x_il8 && sc.KH == 3 && sc.KW == 3 && sc.S == 1 && sc.TY == 4 && sc.y_f16) {      // fp32 interleaved in (2-D tower tensor)
+            if (sc.y_il8) launch_s3<3, 3, 1, true, true, 4, float, _Float16>(grid, ks, per_cu, S(L.s), a, trace);
+            else launch_s3<3, 3, 1, true, false, 4, float, _Float16>(grid, ks, per_cu, S(L.s), a, trace);
+            RT_LAUNCH_CHECK("conv_s3_kernel<float, f16>");
+            return 0;
+        }
+        RT_REQUIRE(!sc.x_il8 && !(sc.y_il8 && sc.x_f16) && sc.TY == 4 && sc.y_f16, "rt_conv_enqueue: fp16-storage variant of the split kernel not instantiated");
+#define RT_S3H(kh, kw, st)                                                                                           \
+    if (!launched && sc.KH == kh && sc.KW == kw && sc.S == st) {                                                     \
+        if (sc.x_f16) launch_s3<kh, kw, st, false, false, 4, _Float16, _Float16>(grid, ks, per_cu, S(L.s), a, trace); \
+        else if (sc.y_il8) launch_s3<kh, kw, st, false, true, 4, float, _Float16>(grid, ks, per_cu, S(L.s), a, trace); \
+        else launch_s3<kh, kw, st, false, false, 4, float, _Float16>(grid, ks, per_cu, S(L.s), a, trace);            \
+        launched = true;                                                                                             \
+    }
+        RT_S3H(3, 3, 1) RT_S3H(3, 3, 2) RT_S3H(1, 1, 1) RT_S3H(1, 2, 1) RT_S3H(2, 1, 1) RT_S3H(2, 2, 1)
+#undef RT_S3H
+    }
+#ifdef RT_EXPERIMENTAL
+    if (!launched && sc.KH == 3 && sc.KW == 3 && sc.S == 1 && sc.TY == 8) {          // 8-row tiles, 8 waves
+        with_bools([&](auto xi, auto yi) { launch_s3<3, 3, 1, xi, yi, 8>(grid, ks, per_cu, S(L.s), a, trace); }, sc.x_il8, sc.y_il8);
+        launched = true;
+    }
+#endif
+#define RT_S3(kh, kw, st)                                                                                                              \
+    if (!launched && sc.KH == kh && sc.KW == kw && sc.S == st) {                                                                       \
+        with_bools([&](auto xi, auto yi) { launch_s3<kh, kw, st, xi, yi>(grid, ks, per_cu, S(L.s), a, trace); }, sc.x_il8, sc.y_il8); \
+        launched = true;                                                                                                               \
+    }
+    RT_S3(3, 3, 1) RT_S3(3, 3, 2) RT_S3(1, 1, 1) RT_S3(1, 2, 1) RT_S3(2, 1, 1) RT_S3(2, 2, 1)
+#undef RT_S3
+    if (!launched) return fail(RT_E_UNSUPPORTED, "conv (split fp16): window %dx%d stride %d not instantiated", sc.KH, sc.KW, sc.S);
+    RT_LAUNCH_CHECK("conv_s3_kernel");
+    return 0;
+}
+
+// conv_f16dw_kernel (conv_f16dw.hip.h): Conv3D 3x3x3 stride 1 between interleaved fp16 tensors, the workgroup walks down the depth axis.
+// taken = false: not its layer, or a launch it declines (the caller goes on to the per-slice kernels)
+int enqueue_f16dw(const Launch& L, const SubConv& sc, rt::ConvArgs& a, bool& taken) {
+    const rtConvPlan* plan = L.plan;
+    if (!(plan->c3d_dw && plan->opt.dw != 0 && sc.KH == 3 && sc.KW == 3 && sc.S == 1 && sc.x_il8 && sc.y_il8 && !sc.zs_dev && sc.y_xstride == 1 &&
+          (!plan->has_resid || sc.r_il8) && (plan->act == RT_ACT_NONE || plan->act == RT_ACT_ELU) && !sc.shift_dev))
+        return 0;
+    using Dw = rt::ConvF16DwCfg;
+    const int dw_tiles_x = (int)rt::cdiv(sc.Wo, Dw::TX), dw_nkb = (int)rt::cdiv(sc.Cout, 32);
+    const int64_t npairs = rt::cdiv(dw_tiles_x * (int)rt::cdiv(sc.Ho, Dw::TY), 2);
+    // depth segments: every segment pays two steps' worth of MFMAs for its neighbours' slices and a prologue, every round of
+    // workgroups over the CUs costs a whole segment -- minimise rounds x (segment + overhead); results do not depend on it.
+    // MI355X, NVSmall half2 (profiles/r05_conv3d_layers.txt): batch 8 -- one segment everywhere (conv3D_2 0.206 ms per pair, two
+    // segments 0.215, four 0.228); batch 1 -- conv3D_2 two segments (0.232; one: 0.340), conv3D_4 four (0.137; one: 0.298).
+    int nseg = plan->opt.dw_nseg;
+    double best = 1e30, fill = 1.0;
+    for (int ns = 1; ns <= sc.nz; ns++) {
+        const int seg = (int)rt::cdiv(sc.nz, ns);
+        if (ns > 1 && seg < 4) break;
+        if ((int)rt::cdiv(sc.nz, seg) != ns || (plan->opt.dw_nseg > 0 && ns != std::min(plan->opt.dw_nseg, sc.nz))) continue;
+        const int64_t wgs = npairs * ns * dw_nkb * L.batch, rounds = rt::cdiv(wgs, (int64_t)device_cus());
+        const double steps = seg + (ns > 1 ? 3.0 : 1.7), cost = (double)rounds * steps;
+        if (cost < best - 1e-9) { best = cost; nseg = ns; fill = (double)wgs / (double)(rounds * device_cus()) * seg / steps; }
+    }
+    // a launch that would leave most of the chip idle or spend its time on segment ends stays with the per-slice kernel (the
+    // 128-channel layers at 12 x 41 x 129: 0.155 against 0.098 ms at batch 1, a tie at batch 8)
+    if (plan->opt.dw < 0 && fill < 0.6) return 0;
+    taken = true;
+    nseg = std::max(1, std::min(nseg, sc.nz));
+    a.tiles_x = dw_tiles_x;
+    a.dw_ntiles = a.tiles_x * (int)rt::cdiv(sc.Ho, Dw::TY);
+    a.dw_cpc = plan->c3d_C / 16;
+    a.nb_inner = dw_nkb;
+    a.dw_seg = (int)rt::cdiv(sc.nz, nseg);
+    a.dw_nseg = (int)rt::cdiv(sc.nz, a.dw_seg);
+    const int64_t gx = npairs * a.dw_nseg * a.nb_inner;
+    RT_REQUIRE(gx < (1ll << 31) && L.batch <= 65535, "rt_conv_enqueue: grid limit exceeded");
+    dim3 gd((unsigned)gx, 1u, (unsigned)L.batch);
+    const bool resident = a.dw_cpc <= 2, elu = plan->act == RT_ACT_ELU;
+    if (plan->opt.trace)        // conv_f16dw_kernel<resident, has_resid, elu>
+        fprintf(stderr, "[rt] conv_f16dw<%d,%d,%d> grid %u x %u segments %d x %d slices, %d chunks per slice\n", resident ? 1 : 0,
+                plan->has_resid ? 1 : 0, elu ? 1 : 0, gd.x, gd.z, a.dw_nseg, a.dw_seg, a.dw_cpc);
+    with_bools([&](auto res, auto hr, auto el) { hipLaunchKernelGGL((rt::conv_f16dw_kernel<res, hr, el>), gd, dim3(512), 0, S(L.s), a); },
+               resident, plan->has_resid, elu);
+    RT_LAUNCH_CHECK("conv_f16dw_kernel");
+    return 0;
+}
+
+// fp16 operands on the matrix cores, both tensors fp16: the depth walk, then four rows per wave, then conv_f16mma_kernel's 4 x 32 tile
+int enqueue_f16mma(const Launch& L, const SubConv& sc, rt::ConvArgs& a, const ConvGrid& g) {
+    const rtConvPlan* plan = L.plan;
+    bool taken = false;
+    if (int rc = enqueue_f16dw(L, sc, a, taken)) return rc;
+    if (taken) return 0;
+    // Conv3D between interleaved fp16 tensors: four output rows per wave, operands reused from registers (conv_f16r4.hip.h) -- the
+    // 4 x 32-tile kernel below reads 2 KB of LDS per MFMA and is LDS-bound at 0.3 of the matrix peak on these layers
+    if (sc.KH == 3 && sc.KW == 3 && sc.S == 1 && sc.x_il8 && sc.y_il8 && !sc.zs_dev && sc.TY == 4 && sc.y_xstride == 1 &&
+        (plan->opt.r4 > 0 || (plan->opt.r4 < 0 && plan->is_conv3d && sc.Ho >= 12))) {
+        dim3 g4 = g.fold(dim3((unsigned)(a.tiles_x * (int)rt::cdiv(sc.Ho, rt::ConvF16R4Cfg::TY)), g.grid.y, g.grid.z));
+        if (plan->opt.trace) fprintf(stderr, "[rt] conv_f16r4 grid %u x %u x %u\n", g4.x, g4.y, g4.z);
+        hipLaunchKernelGGL(rt::conv_f16r4_kernel, g4, dim3(256), 0, S(L.s), a);
+        RT_LAUNCH_CHECK("conv_f16r4_kernel");
+        return 0;
+    }
+    if (plan->opt.trace)        // (after the two walks above: this line names the conv_f16mma_kernel launches below)
+        fprintf(stderr, "[rt] conv_f16mma %dx%d s%d rows %d il8 x%d y%d r%d grid %u x %u x %u\n", sc.KH, sc.KW, sc.S, sc.TY, sc.x_il8,
+                sc.y_il8, sc.r_il8, g.grid.x, g.grid.y, g.grid.z);
+    const dim3 grid = g.fold(g.grid);
+    if (sc.KH == 3 && sc.KW == 3 && sc.S == 1 && sc.TY == 4) {     // the tower layers, every pair of tensor layouts
+        with_bools([&](auto xi, auto yi) { hipLaunchKernelGGL((rt::conv_f16mma_kernel<3, 3, 1, xi, yi, 4>), grid, dim3(256), 0, S(L.s), a); },
+                   sc.x_il8, sc.y_il8);
+        RT_LAUNCH_CHECK("conv_f16mma_kernel<3,3,1>");
+        return 0;
+    }
+    if (sc.KH == 3 && sc.KW == 3 && sc.S == 2 && sc.TY == 4 && (sc.x_il8 || sc.y_il8)) {      // stride-2 Conv3D on interleaved 4-D tensors
+        if (sc.x_il8 && sc.y_il8) hipLaunchKernelGGL((rt::conv_f16mma_kernel<3, 3, 2, true, true>), grid, dim3(256), 0, S(L.s), a);
+        else if (sc.x_il8) hipLaunchKernelGGL((rt::conv_f16mma_kernel<3, 3, 2, true, false>), grid, dim3(256), 0, S(L.s), a);
+        else hipLaunchKernelGGL((rt::conv_f16mma_kernel<3, 3, 2, false, true>), grid, dim3(256), 0, S(L.s), a);
+        RT_LAUNCH_CHECK("conv_f16mma_kernel<3,3,2>");
+        return 0;
+    }
+    if (sc.KH == 2 && sc.KW == 2 && sc.S == 1 && sc.TY == 4 && sc.x_il8) {      // phases of a transposed 3-D convolution on interleaved input
+        if (sc.y_il8) hipLaunchKernelGGL((rt::conv_f16mma_kernel<2, 2, 1, true, true>), grid, dim3(256), 0, S(L.s), a);
+        else hipLaunchKernelGGL((rt::conv_f16mma_kernel<2, 2, 1, true, false>), grid, dim3(256), 0, S(L.s), a);
+        RT_LAUNCH_CHECK("conv_f16mma_kernel<2,2,1,il>");
+        return 0;
+    }
+    RT_REQUIRE(!(sc.x_il8 || sc.y_il8 || sc.r_il8) && sc.TY == 4, "rt_conv_enqueue: fp16-arithmetic variant not instantiated");
+    const char* launched = nullptr;
+#define RT_F16CASE(kh, kw, st)                                                                       \
+    if (!launched && sc.KH == kh && sc.KW == kw && sc.S == st) {                                     \
+        hipLaunchKernelGGL((rt::conv_f16mma_kernel<kh, kw, st>), grid, dim3(256), 0, S(L.s), a);     \
+        launched = "conv_f16mma_kernel<" #kh "," #kw "," #st ">";                                    \
+    }
+    RT_F16CASE(3, 3, 2) RT_F16CASE(1, 1, 1) RT_F16CASE(1, 2, 1) RT_F16CASE(2, 1, 1) RT_F16CASE(2, 2, 1)
+#undef RT_F16CASE
+    if (!launched) return fail(RT_E_UNSUPPORTED, "conv (fp16 arithmetic): window %dx%d stride %d not instantiated", sc.KH, sc.KW, sc.S);
+    RT_LAUNCH_CHECK(launched);
+    return 0;
+}
+
+// conv_wino_f32_kernel (conv_wino.hip.h): Winograd F(2x2, 3x3), exact fp32 or fp16 storage
+int enqueue_wino(const Launch& L, const SubConv& sc, const rt::ConvArgs& a, const ConvGrid& g) {
+    const dim3 grid = g.grid;
+    RT_REQUIRE(!sc.zs_dev && sc.y_xstride == 1, "rt_conv_enqueue: Winograd kernel takes uniform, x-contiguous slices only");
+    if (sc.x_f16 || sc.y_f16) {
+        RT_REQUIRE(sc.x_f16 && sc.y_f16, "rt_conv_enqueue: the Winograd kernel takes fp16 on both sides or on neither");
+        hipLaunchKernelGGL((rt::conv_wino_f32_kernel<4, _Float16, _Float16>), grid, dim3(256), 0, S(L.s), a);
+    }
+#ifdef RT_EXPERIMENTAL
+    else if (sc.NW == 8) {
+        RT_REQUIRE(!(sc.x_il8 || sc.y_il8 || sc.r_il8), "rt_conv_enqueue: interleaved tensors need the 4-wave Winograd tile");
+        hipLaunchKernelGGL((rt::conv_wino_f32_kernel<8>), grid, dim3(512), 0, S(L.s), a);
+    }
+#else
+    else if (sc.NW != 4) return fail(RT_E_UNSUPPORTED, "rt_conv_enqueue: Winograd kernel: 4-wave tile (8 waves: RT_EXPERIMENTAL builds)");
+#endif
+    else if (sc.x_il8 && sc.y_il8) hipLaunchKernelGGL((rt::conv_wino_f32_kernel<4, float, float, true, true>), grid, dim3(256), 0, S(L.s), a);
+    else if (sc.x_il8) hipLaunchKernelGGL((rt::conv_wino_f32_kernel<4, float, float, true, false>), grid, dim3(256), 0, S(L.s), a);
+    else if (sc.y_il8) hipLaunchKernelGGL((rt::conv_wino_f32_kernel<4, float, float, false, true>), grid, dim3(256), 0, S(L.s), a);
+    else if (sc.r_il8) hipLaunchKernelGGL((rt::conv_wino_f32_kernel<4, float, float, false, false, true>), grid, dim3(256), 0, S(L.s), a);
+    else hipLaunchKernelGGL((rt::conv_wino_f32_kernel<4>), grid, dim3(256), 0, S(L.s), a);
+    RT_LAUNCH_CHECK("conv_wino_f32_kernel");
+    return 0;
+}
+
+// Every convolution launch of every model: the sub-plans of a plan, each on the launcher of its kernel family.  The ORDER of the chain is
+// behaviour: a sub-plan may carry several of the flags
+int enqueue_conv(const Launch& L, void* workspace, size_t workspace_bytes) {
+    const rtConvPlan* plan = L.plan;
+    RT_REQUIRE(plan && L.x && L.y, "rt_conv_enqueue: null pointer");
+    RT_REQUIRE(L.batch > 0, "rt_conv_enqueue: batch must be positive");
+    RT_REQUIRE(!plan->has_resid || L.residual || plan->rb_w1_dev, "rt_conv_enqueue: plan expects a residual tensor");
+    RT_REQUIRE(!plan->rb_w1_dev || !L.residual || L.residual == L.x, "rt_conv_enqueue: a residual block's skip connection is its input tensor");
+    std::call_once(plan->env_once, [&] { plan->opt = read_conv_knobs(); });      // execution contexts of one engine share the plan and may launch it from different threads
+    if (fold_factor_active(plan)) return enqueue_fold_factor(plan, L.x, L.y, L.batch, workspace, workspace_bytes, L.s, L.hints);
+    for (size_t i = 0; i < plan->subs.size(); i++) {
+        const SubConv& sc = plan->subs[i];
+        if (sc.small3d) {
+            if (int rc = enqueue_small3d(L, sc)) return rc;
+            continue;
+        }
+        rt::ConvArgs a = conv_args(L, sc);
+        int rc = 0;
+        bool took_next = false;            // the launch covered sub-plan i + 1 too (two depth classes of a transposed layer in one walk)
+        ConvGrid g;
+        if (sc.dp4 && sc.split3) rc = enqueue_deconv_s3p(L, sc, a);
+        else if (sc.dp4) rc = enqueue_deconv_f16p(L, sc, a, took_next);
+        else if ((rc = conv_grid(L, sc, a, g)) != 0) return rc;
+        else if (sc.direct) rc = enqueue_direct(L, sc, a, g);
+#ifdef RT_EXPERIMENTAL
+        else if (sc.s3p) rc = enqueue_s3p(L, sc, a, g);
+#endif
+        else if (sc.rb) rc = enqueue_resblock(L, sc, a, g);
+        else if (sc.s3first) rc = enqueue_s3first(L, sc, a, g);
+        else if (sc.split3) rc = enqueue_split3(L, sc, a, g);
+        else if (sc.f16first) rc = enqueue_f16first(L, sc, a, g);
+        else if (sc.f16mma) rc = enqueue_f16mma(L, sc, a, g);
+        else if (sc.wino) rc = enqueue_wino(L, sc, a, g);
+        else rc = launch_sub(sc, a, g.grid, S(L.s));
+        if (rc) return rc;
+        if (took_next) i++;
+    }
+    return 0;
+}
+}  // namespace
+
 extern "C" int rt_conv_enqueue_twin_input(const rtConvPlan* plan, const void* x, const void* x2, void* y, int batch, rtStream s, int hints) {
     RT_REQUIRE(plan && x && x2 && y && batch > 0, "rt_conv_enqueue_twin_input: bad arguments");
     if (!rt_conv_plan_supports_twin_input(plan)) return fail(RT_E_UNSUPPORTED, "rt_conv_enqueue_twin_input: only the first-layer kernels read two input tensors");
-    tl_twin_x2 = x2; tl_twin_from = batch;
-    const int rc = rt_conv_enqueue_ws(plan, x, y, nullptr, 2 * batch, nullptr, 0, s, hints);
-    tl_twin_x2 = nullptr; tl_twin_from = 0;
-    return rc;
+    return enqueue_conv(Launch{plan, x, x2, batch, y, nullptr, 2 * batch, s, hints}, nullptr, 0);
 }
 
 extern "C" int rt_conv_enqueue_ws(const rtConvPlan* plan, const void* x, void* y, const void* residual, int batch, void* workspace,
                                   size_t workspace_bytes, rtStream s, int hints) {
-    RT_REQUIRE(plan && x && y, "rt_conv_enqueue: null pointer");
-    RT_REQUIRE(batch > 0, "rt_conv_enqueue: batch must be positive");
-    RT_REQUIRE(!plan->has_resid || residual || plan->rb_w1_dev, "rt_conv_enqueue: plan expects a residual tensor");
-    RT_REQUIRE(!plan->rb_w1_dev || !residual || residual == x, "rt_conv_enqueue: a residual block's skip connection is its input tensor");
-    std::call_once(plan->env_once, [&] {        // execution contexts of one engine share the plan and may launch it from different threads
-        plan->opt_xcd = env_int("RT_CONV_XCD", 1); plan->opt_trace = env_int("RT_CONV_TRACE", 0);
-        plan->opt_rb_tiles = exp_knob("RT_RB_TILES", 0); plan->opt_rbs_seg = env_int("RT_RBS_SEG", 0); plan->opt_ksplit = env_int("RT_S3_KSPLIT", -1);
-        plan->opt_s3p_grid = env_int("RT_S3P_GRID", 0);
-        plan->opt_zinner = env_int("RT_Z_INNER", 1);     // 3-D launches: depth slices fastest inside a tile (ConvArgs::z_inner); 0 = z outermost
-        plan->opt_nbinner = env_int("RT_NB_INNER", 1);  // 3-D launches: blocks of 32 output channels fastest (ConvArgs::nb_inner); 0 = grid.y
-        plan->opt_dw = env_int("RT_F16_DW", -1);         // -1: where it applies (3x3x3 stride-1 Conv3D between interleaved fp16 tensors), 0: never
-        plan->opt_dw_nseg = env_int("RT_DW_NSEG", 0);   // depth segments per tile pair (0: chosen from the grid)
-        plan->opt_fold_u = env_int("RT_FOLD_U", 2);           // factored cost-volume fold: depth slices per trip of the combining pass (MI355X, NVSmall b8: 1: 0.84, 2: 0.68, 4: 1.07 ms)
-        plan->opt_f16p_classes = env_int("RT_F16P_CLASSES", 1);   // ... 1: both depth classes (even / odd output depths) in one walk, 0: a launch per class
-        plan->opt_f16p_walk = env_int("RT_F16P_WALK", -1);        // transposed fp16 layers, four phases per workgroup: -1 walk down the class's depths (segments chosen), 0 one depth per workgroup, n > 0: n segments
-        plan->opt_small_walk = env_int("RT_SMALL_IL_WALK", -1);   // last transposed layer on interleaved fp16 input: 0 = one depth block per workgroup
-        plan->opt_r4 = env_int("RT_F16_R4", -1);         // -1: where it pays (3-D plans), 0: never, 1: every 3x3 stride-1 fp16 launch on interleaved tensors
-    });
-    if (fold_factor_active(plan)) return enqueue_fold_factor(plan, x, y, batch, workspace, workspace_bytes, s, hints);
-    bool skip_sub = false;               // the previous sub-plan's launch covered this one too (two depth classes of a transposed layer in one walk)
-    for (const SubConv& sc : plan->subs) {
-        if (skip_sub) { skip_sub = false; continue; }
-        if (sc.small3d) {
-            rt::Deconv3dSmallArgs a = sc.s3;
-            a.x = static_cast<const float*>(x); a.y = static_cast<float*>(y); a.w = sc.w_dev; a.bias = plan->bias_dev;
-            a.resid = plan->has_resid ? static_cast<const float*>(residual) : nullptr;
-            a.act = plan->act; a.x_bstride = plan->x_bstride; a.y_bstride = plan->y_bstride;
-            const int64_t gz = (int64_t)batch * a.Mz;
-            RT_REQUIRE(gz <= 65535 && (a.Hx + 1) / 2 <= 65535, "rt_conv_enqueue: grid limit exceeded");
-            dim3 grid((unsigned)rt::cdiv((a.Wx + 1) / 2, 256), (unsigned)((a.Hx + 1) / 2), (unsigned)gz);
-            // deconv3d_s2_small_kernel<C, second template argument, TIN, TOUT> -- the branches below, in their order
-            if (plan->opt_trace && !(sc.small3d == 1 && sc.x_il8))
-                fprintf(stderr, "[rt] deconv3d_s2_small<%d,%d,%s,%s> grid %u x %u x %u\n", a.C == 1 ? 1 : 2, sc.small3d == 1 ? 1 : 0,
-                        sc.x_f16 ? "f16" : "f32", (sc.small3d == 2 && sc.x_f16 && sc.y_f16) ? "f16" : "f32", grid.x, grid.y, grid.z);
-            if (sc.small3d == 2 && sc.x_f16) {          // half2 mode: fp16 activations in, fp32 (binding) or fp16 out
-                if (sc.y_f16) {
-                    if (a.C == 1) hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<1, false, _Float16, _Float16>), grid, dim3(256), 0, S(s), a);
-                    else hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<2, false, _Float16, _Float16>), grid, dim3(256), 0, S(s), a);
-                } else {
-                    if (a.C == 1) hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<1, false, _Float16, float>), grid, dim3(256), 0, S(s), a);
-                    else hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<2, false, _Float16, float>), grid, dim3(256), 0, S(s), a);
-                }
-            } else if (sc.small3d == 1 && sc.x_f16 && sc.x_il8) {     // ... with a channel-interleaved (K/8, D, H, W, 8) input: on the matrix cores
-                a.w = static_cast<const float*>(sc.small_il_dev);
-                const int groups = (int)rt::cdiv((a.Wx + 1) / 2, 16);
-                RT_REQUIRE(batch <= 65535, "rt_conv_enqueue: grid limit exceeded");
-                const int rowpairs = (int)rt::cdiv((a.Hx + 1) / 2, 2);
-                if (plan->softarg) {
-                    // the walk is the soft-argmax's reduction axis: one segment, y = the (batch, 1, Hx, Wx) map
-                    RT_REQUIRE(a.K == 32 && a.C == 1 && !a.resid && rowpairs <= 65535, "rt_conv_enqueue: plan lost the form its fused soft-argmax needs");
-                    a.y_bstride = (int64_t)a.Hx * a.Wx;
-                    dim3 gw((unsigned)rt::cdiv(groups, 4), (unsigned)rowpairs, (unsigned)batch);
-                    if (plan->opt_trace) fprintf(stderr, "[rt] deconv3d_s2_ilw<%d> grid %u x %u x %u segments 1 x %d\n", plan->softarg == 2 ? 2 : 1, gw.x, gw.y, gw.z, a.Mz);
-                    if (plan->softarg == 2) hipLaunchKernelGGL(rt::deconv3d_s2_ilw_kernel<2>, gw, dim3(256), 0, S(s), a, a.Mz, 1);
-                    else hipLaunchKernelGGL(rt::deconv3d_s2_ilw_kernel<1>, gw, dim3(256), 0, S(s), a, a.Mz, 1);
-                } else if (a.K == 32 && plan->opt_small_walk != 0) {
-                    // the depth walk (deconv3d_s2_ilw_kernel): segments long enough to pay for their prologue (>= 8 depth blocks), as many as
-                    // it takes to give every SIMD about two waves
-                    const int64_t waves = (int64_t)groups * rowpairs * batch;
-                    int nseg = (int)std::min<int64_t>(std::max<int64_t>(1, rt::cdiv((int64_t)8 * device_cus(), waves)), std::max(1, a.Mz / 8));
-                    const int seg_len = (int)rt::cdiv(a.Mz, nseg);
-                    nseg = (int)rt::cdiv(a.Mz, seg_len);
-                    RT_REQUIRE(rowpairs <= 65535, "rt_conv_enqueue: grid limit exceeded");
-                    dim3 gw((unsigned)(rt::cdiv(groups, 4) * nseg), (unsigned)rowpairs, (unsigned)batch);
-                    if (plan->opt_trace) fprintf(stderr, "[rt] deconv3d_s2_ilw<0> grid %u x %u x %u segments %d x %d\n", gw.x, gw.y, gw.z, nseg, seg_len);
-                    hipLaunchKernelGGL(rt::deconv3d_s2_ilw_kernel<0>, gw, dim3(256), 0, S(s), a, seg_len, nseg);
-                } else {
-                    dim3 g2((unsigned)(rt::cdiv(groups, 4 * rt::kSmallIlIters) * a.Mz), (unsigned)rowpairs, (unsigned)batch);
-                    if (plan->opt_trace) fprintf(stderr, "[rt] deconv3d_s2_il grid %u x %u x %u\n", g2.x, g2.y, g2.z);
-                    hipLaunchKernelGGL(rt::deconv3d_s2_il_kernel, g2, dim3(256), 0, S(s), a);
-                }
-            } else if (sc.small3d == 1 && !sc.x_f16 && sc.x_il8) {    // fp32 engines: (K/4, D, H, W, 4) in, split form on the matrix cores
-                RT_REQUIRE(sc.small_il_dev && sc.small_il_f32, "rt_conv_enqueue: interleaved fp32 input without its weight operands (rt_conv_plan_set_layouts)");
-                a.w = static_cast<const float*>(sc.small_il_dev);
-                const int groups = (int)rt::cdiv((a.Wx + 1) / 2, 16);
-                RT_REQUIRE(batch <= 65535, "rt_conv_enqueue: grid limit exceeded");
-                dim3 g2((unsigned)(rt::cdiv(groups, 4 * rt::kSmallIlIters) * a.Mz), (unsigned)rt::cdiv((a.Hx + 1) / 2, 2), (unsigned)batch);
-                if (plan->opt_trace) fprintf(stderr, "[rt] deconv3d_s2_il4 grid %u x %u x %u\n", g2.x, g2.y, g2.z);
-                hipLaunchKernelGGL(rt::deconv3d_s2_il4_kernel, g2, dim3(256), 0, S(s), a);
-            } else if (sc.small3d == 1 && sc.x_f16) {   // 3-D last layer in half2 mode: fp16 (K,D,H,W) in, fp32 volume out
-                if (a.C == 1) hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<1, true, _Float16, float>), grid, dim3(256), 0, S(s), a);
-                else hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<2, true, _Float16, float>), grid, dim3(256), 0, S(s), a);
-            } else if (sc.small3d == 2) {
-                if (a.C == 1) hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<1, false>), grid, dim3(256), 0, S(s), a);
-                else hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<2, false>), grid, dim3(256), 0, S(s), a);
-            } else {
-                if (a.C == 1) hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<1, true>), grid, dim3(256), 0, S(s), a);
-                else hipLaunchKernelGGL((rt::deconv3d_s2_small_kernel<2, true>), grid, dim3(256), 0, S(s), a);
-            }
-            RT_LAUNCH_CHECK("deconv3d_s2_small_kernel");
-            continue;
-        }
-        rt::ConvArgs a;
-        a.z_inner = 0; a.nb_inner = 0;
-        a.x = static_cast<const float*>(x);
-        a.x2 = static_cast<const float*>(tl_twin_x2); a.x2_from = tl_twin_from;      // rt_conv_enqueue_twin_input (first layers only)
-        a.y = static_cast<float*>(y);
-        a.w = sc.w_dev;
-        a.bias = plan->bias_dev;
-        a.zeros = plan->zeros_dev;
-        a.dbg = nullptr;
-#ifdef RT_KERNEL_TIMING
-        if (const char* e = getenv("RT_DBG_PTR")) a.dbg = (unsigned long long*)strtoull(e, nullptr, 0);
-#endif
-        a.resid = plan->has_resid ? static_cast<const float*>(residual) : nullptr;
-        a.ch_off = sc.choff_dev;
-        a.ch_shift = sc.shift_dev;
-        a.w_exact = plan->w_f16;
-        a.zs = sc.zs_dev;
-        a.CinPad = sc.CinPad; a.Cout = sc.Cout;
-        a.Hi = sc.Hi; a.Wi = sc.Wi; a.Ho = sc.Ho; a.Wo = sc.Wo;
-        a.x_pitch = sc.x_pitch ? sc.x_pitch : sc.Wi;
-        a.pad_y = sc.pad_y; a.pad_x = sc.pad_x; a.nz = sc.nz;
-        a.tiles_x = (int)rt::cdiv(sc.Wo, 32 * sc.TXW);
-        a.act = plan->act;
-        a.xcd_order = plan->opt_xcd;
-        a.x_bstride = plan->x_bstride; a.y_bstride = plan->y_bstride;
-        a.y_cstride = sc.y_cstride; a.y_zstride = sc.y_zstride; a.y_off = sc.y_off;
-        // Conv3D writing a channel-major interleaved tensor (K/8, D, H, W, 8): a depth slice is 8 * H * W elements apart
-        if (plan->is_conv3d && !plan->c3d_dchw && sc.y_il8) a.y_zstride = 8 * sc.y_zstride;
-        a.y_ystride = sc.y_ystride; a.y_xstride = sc.y_xstride;
-        a.r_cstride = sc.r_cstride ? sc.r_cstride : sc.y_cstride;
-        a.r_bstride = plan->r_bstride ? plan->r_bstride : plan->y_bstride;
-        a.r_il8 = sc.r_il8;
-        a.batch = batch; a.cin_real = sc.cin_real; a.x_cstride = (int64_t)sc.Hi * a.x_pitch;
-        if (sc.dp4 && sc.split3) {     // fp32 tensors: four phases per workgroup in split-fp16 form (deconv_s3p.hip.h), planar input and output
-            a.tiles_x = (int)rt::cdiv(sc.Wi, 32);
-            const int tiles = a.tiles_x * (int)rt::cdiv(sc.Hi, 4), nblk = (int)rt::cdiv(sc.Cout, 32);
-            RT_REQUIRE(!sc.x_il8 && !sc.x_f16 && !sc.y_f16, "rt_conv_enqueue: the fp32 four-phase transposed kernel takes a planar fp32 input and writes fp32");
-            RT_REQUIRE((int64_t)batch * sc.nz <= 65535, "rt_conv_enqueue: grid limit exceeded");
-            RT_REQUIRE(sc.y_cstride * (int64_t)sc.Cout < (1ll << 29), "rt_conv_enqueue: output sample exceeds 2 GB (32-bit buffer offsets)");
-            dim3 g((unsigned)tiles, (unsigned)nblk, (unsigned)(batch * sc.nz));
-            if (plan->opt_trace) fprintf(stderr, "[rt] deconv_s3p<%d> r%d grid %u x %u x %u\n", sc.y_il8 ? 1 : 0, sc.r_il8, g.x, g.y, g.z);
-            if (sc.y_il8) hipLaunchKernelGGL(rt::deconv_s3p_kernel<true>, g, dim3(256), 0, S(s), a);
-            else hipLaunchKernelGGL(rt::deconv_s3p_kernel<false>, g, dim3(256), 0, S(s), a);
-            RT_LAUNCH_CHECK("deconv_s3p_kernel");
-            continue;
-        }
-        if (sc.dp4) {          // transposed 3-D convolution, four phases per workgroup (deconv_f16p.hip.h): tiles of the INPUT grid, one z per output depth
-            a.tiles_x = (int)rt::cdiv(sc.Wi, 32);
-            const int tiles = a.tiles_x * (int)rt::cdiv(sc.Hi, 4), nblk = (int)rt::cdiv(sc.Cout, 32);
-            RT_REQUIRE(sc.x_il8 && sc.y_il8 && sc.x_f16 && sc.y_f16, "rt_conv_enqueue: the four-phase transposed kernel takes interleaved fp16 tensors");
-            a.z_inner = plan->opt_zinner != 0 ? 1 : 0;
-            RT_REQUIRE(batch <= 65535 && (int64_t)batch * sc.nz <= 65535, "rt_conv_enqueue: grid limit exceeded");
-            dim3 g = a.z_inner ? dim3((unsigned)(tiles * sc.nz), (unsigned)nblk, (unsigned)batch) : dim3((unsigned)tiles, (unsigned)nblk, (unsigned)(batch * sc.nz));
-            if (plan->opt_f16p_walk != 0 && (!plan->has_resid || sc.r_il8)) {       // (a planar skip tensor -- not what the executor uses -- stays with the per-depth kernel)
-                // the walk (deconv_f16pw_kernel): a workgroup keeps its tile and takes a segment of the class's output depths.  Segments as
-                // long as the grid allows: cost = rounds over the chip's 3 workgroups per CU x (slices per segment + one slice's worth of
-                // fill and drain)
-                // Both depth classes in ONE walk (slice m of the even class, then slice m of the odd one: their input slices are the same and
-                // the next): the second sub-plan rides along when it is the same launch in everything but weights, slices and gather table
-                rt::DeconvWalkB wb{};
-                const SubConv* sb = (&sc == &plan->subs[0] && plan->subs.size() == 2) ? &plan->subs[1] : nullptr;
-                if (sb && plan->opt_f16p_classes != 0 && sb->dp4 && sb->f16mma && sb->x_il8 && sb->y_il8 && sb->x_f16 && sb->y_f16 && sb->r_il8 == sc.r_il8 &&
-                    sb->Hi == sc.Hi && sb->Wi == sc.Wi && sb->Ho == sc.Ho && sb->Wo == sc.Wo && sb->Cout == sc.Cout && sb->x_pitch == sc.x_pitch &&
-                    sb->y_cstride == sc.y_cstride && sb->y_ystride == sc.y_ystride && sb->r_cstride == sc.r_cstride) {
-                    wb.w = static_cast<const float*>(sb->w_dev); wb.zs = sb->zs_dev; wb.ch_off = sb->choff_dev; wb.CinPad = sb->CinPad; wb.nz = sb->nz;
-                    skip_sub = true;
-                }
-                const int nzw = std::max(sc.nz, wb.zs ? wb.nz : 0);                             // slice indices of the walk
-                const double per_m = wb.zs ? (double)(sc.CinPad + wb.CinPad) / sc.CinPad : 1.0; // work per slice index, in slices of this class
-                const int64_t slots = (int64_t)3 * device_cus(), base = (int64_t)tiles * nblk * batch;
-                // (among segmentations within 5 % of the cheapest, the one with the most segments: rounds of long walks do not stay in step and
-                //  their tail is a whole walk long -- NVSmall deconv3D_2 at batch 8: 1 segment 1.31 ms, 4 segments 1.26, both "cost" 146-152)
-                int nseg = 1;
-                double best = 1e30;
-                auto seg_cost = [&](int ns) {
-                    const int seg = (int)rt::cdiv(nzw, ns);
-                    return (int)rt::cdiv(nzw, seg) != ns ? 1e30 : (double)rt::cdiv(base * ns, slots) * (seg * per_m + 1.0);
-                };
-                for (int ns = 1; ns <= nzw; ns++) best = std::min(best, seg_cost(ns));
-                for (int ns = 1; ns <= nzw; ns++)
-                    if (seg_cost(ns) <= 1.05 * best) nseg = ns;
-                if (plan->opt_f16p_walk > 0) nseg = std::min(plan->opt_f16p_walk, nzw);            // (RT_F16P_WALK=<n>: n segments)
-                a.dw_seg = (int)rt::cdiv(nzw, nseg); a.dw_nseg = nzw; a.dw_cpc = sc.nz; a.nz = (int)rt::cdiv(nzw, a.dw_seg);
-                RT_REQUIRE((int64_t)batch * a.nz <= 65535, "rt_conv_enqueue: grid limit exceeded");
-                dim3 gw = a.z_inner ? dim3((unsigned)(tiles * a.nz), (unsigned)nblk, (unsigned)batch) : dim3((unsigned)tiles, (unsigned)nblk, (unsigned)(batch * a.nz));
-                if (plan->opt_trace) fprintf(stderr, "[rt] deconv_f16pw grid %u x %u x %u, %d slice indices per segment, %d class(es)\n", gw.x, gw.y, gw.z, a.dw_seg, wb.zs ? 2 : 1);
-                hipLaunchKernelGGL(rt::deconv_f16pw_kernel, gw, dim3(256), 0, S(s), a, wb);
-                RT_LAUNCH_CHECK("deconv_f16pw_kernel");
-                continue;
-            }
-            if (plan->opt_trace) fprintf(stderr, "[rt] deconv_f16p grid %u x %u x %u\n", g.x, g.y, g.z);
-            hipLaunchKernelGGL(rt::deconv_f16p_kernel, g, dim3(256), 0, S(s), a);
-            RT_LAUNCH_CHECK("deconv_f16p_kernel");
-            continue;
-        }
-        const int tiles_y = (int)rt::cdiv(sc.Ho, sc.TY);
-        const int64_t gz = (int64_t)batch * sc.nz;
-        // split-fp16 / fp16-operand launches of 3-D plans fold the z-slices into grid.x, z fastest (conv_mfma.hip.h: ConvArgs::z_inner)
-        // (fp16-operand launches on interleaved tensors only: measured on ResNet-18 3D fp32 the planar split kernel is 3 % SLOWER with z fastest,
-        //  8.56 vs 8.27 ms per pair -- RT_Z_INNER=2 folds those too)
-        const bool zin = sc.nz > 1 && plan->opt_zinner != 0 && (sc.f16mma || (sc.split3 && plan->opt_zinner == 2)) &&
-                         (int64_t)rt::cdiv(sc.Wo, 32 * sc.TXW) * rt::cdiv(sc.Ho, sc.TY) * sc.nz < (1ll << 30);
-        a.z_inner = zin ? 1 : 0;
-        // ... and 3-D launches with several blocks of 32 output channels fold those in as well, fastest of all (ConvArgs::nb_inner)
-        int nb_fold = 0;
-        auto zfold = [&](dim3 g) {
-            if (zin) g = dim3(g.x * (unsigned)sc.nz, g.y, (unsigned)batch);
-            return nb_fold ? dim3(g.x * g.y, 1u, g.z) : g;
-        };
-        RT_REQUIRE(zin ? batch <= 65535 : gz <= 65535, "rt_conv_enqueue: batch * depth = %lld exceeds the grid limit", (long long)gz);
-        RT_REQUIRE(sc.y_cstride * (int64_t)sc.Cout < (1ll << 29), "rt_conv_enqueue: output sample exceeds 2 GB (32-bit buffer offsets)");
-        if (sc.direct) {
-            RT_REQUIRE(sc.Ho <= 65535, "rt_conv_enqueue: output too tall for the direct kernel");
-            dim3 dgrid((unsigned)rt::cdiv(sc.Wo, 256), (unsigned)sc.Ho, (unsigned)gz);
-            bool launched = false;
-#define RT_DIRECT(co, kh, kw)                                                                                         \
-    if (!launched && sc.Cout <= co && sc.KH == kh && sc.KW == kw) {                                                   \
-        hipLaunchKernelGGL((rt::conv_direct_f32_kernel<co, kh, kw>), dgrid, dim3(256), 0, S(s), a, sc.S, sc.cin_real); \
-        launched = true;                                                                                              \
-    }
-            RT_DIRECT(1, 1, 1) RT_DIRECT(1, 1, 2) RT_DIRECT(1, 2, 1) RT_DIRECT(1, 2, 2) RT_DIRECT(1, 3, 3) RT_DIRECT(1, 5, 5)
-            RT_DIRECT(2, 1, 1) RT_DIRECT(2, 1, 2) RT_DIRECT(2, 2, 1) RT_DIRECT(2, 2, 2) RT_DIRECT(2, 3, 3) RT_DIRECT(2, 5, 5)
-#undef RT_DIRECT
-            if (!launched) return fail(RT_E_UNSUPPORTED, "conv (direct): window %dx%d not instantiated", sc.KH, sc.KW);
-            RT_LAUNCH_CHECK("conv_direct_f32_kernel");
-            continue;
-        }
-#ifdef RT_EXPERIMENTAL
-        if (sc.s3p) {
-            // persistent: one 8-wave workgroup per CU walks a contiguous range of tiles (RT_S3P_GRID: test knob)
-            const int64_t T = (int64_t)a.tiles_x * tiles_y * batch;
-            int64_t g = std::min<int64_t>(T, (plan->opt_s3p_grid > 0 ? plan->opt_s3p_grid : device_cus()));
-            if (g >= 8) g -= g % 8;
-            dim3 pgrid((unsigned)std::max<int64_t>(g, 1));
-            if (plan->opt_trace)
-                fprintf(stderr, "[rt] conv_s3p x%d y%d r%d tiles %lld grid %u\n", sc.x_il8, sc.y_il8, sc.r_il8, (long long)T, pgrid.x);
-            if (sc.x_il8 && sc.y_il8) hipLaunchKernelGGL((rt::conv_s3p_kernel<8, true, true>), pgrid, dim3(512), 0, S(s), a);
-            else if (sc.x_il8) hipLaunchKernelGGL((rt::conv_s3p_kernel<8, true, false>), pgrid, dim3(512), 0, S(s), a);
-            else if (sc.y_il8) hipLaunchKernelGGL((rt::conv_s3p_kernel<8, false, true>), pgrid, dim3(512), 0, S(s), a);
-            else hipLaunchKernelGGL((rt::conv_s3p_kernel<8, false, false>), pgrid, dim3(512), 0, S(s), a);
-            RT_LAUNCH_CHECK("conv_s3p_kernel");
-            continue;
-        }
-#endif
-        dim3 grid((unsigned)(a.tiles_x * tiles_y), (unsigned)rt::cdiv(sc.Cout, 32 * sc.NBW), (unsigned)gz);
-        if (!plan->is2d && grid.y > 1 && plan->opt_nbinner != 0 && (sc.f16mma || sc.split3) && !sc.rb && sc.NBW == 1 &&
-            (int64_t)grid.x * grid.y * (zin ? sc.nz : 1) < (1ll << 30))
-            nb_fold = (int)grid.y;
-        a.nb_inner = nb_fold;
-        if (sc.rb) {
-            rt::RBArgs ra;
-            ra.c = a;
-            ra.c.resid = static_cast<const float*>(x);          // the block's input is its skip connection
-            ra.c.r_cstride = a.x_cstride; ra.c.r_bstride = plan->x_bstride; ra.c.r_il8 = sc.x_il8;
-            ra.w1 = plan->rb_w1_dev; ra.bias1 = plan->rb_bias1_dev; ra.act1 = plan->rb_act1; ra.cmid = plan->rb_cmid; ra.seg = 0;
-            // 32 -> 32 -> 32 channels, ELU after both, on interleaved tensors (the feature towers): the streaming form, strips of 30 columns x
-            // segments of 16 rows (conv_rbs.hip.h); everything else: one 4 x 32 tile per workgroup
-            if (sc.x_il8 && sc.y_il8 && plan->cin == 32 && plan->rb_cmid == 32 && sc.Cout == 32 && plan->rb_act1 == 1 && plan->act == 1 &&
-                plan->opt_rb_tiles == 0) {
-                ra.c.tiles_x = (int)rt::cdiv(sc.Wo, rt::S3RBSCfg::SW);
-                // rows per workgroup: the pipeline's fill and drain steps and the prologue are paid per segment, so longer segments
-                // cost fewer CU-cycles per row; shorter ones fill more CUs of an otherwise idle GPU (RT_RBS_SEG, default: see DESIGN.md 4.4)
-                // Measured in the running network (ResNet-18 2D, 1257x369, four contexts): 16 rows 2129, 24: 2178, 32: 2185, 48: 2067,
-                // 64: 1957 pairs/s (two launches of the layer-by-layer kernels: 2057); alone 16 rows are fastest (24.5 vs 32.4 us).
-                // Round 3, siamese batch-2 launches, six one-stream contexts: 32 rows 2315, 48: 2432, 64: 2457-2539, 96: 2441, 128: 2305 pairs/s;
-                // one context, synchronous execute(): 32 rows 0.60 ms per pair, 64: 0.74-0.76 ms.  So: throughput hint -> 64 rows while
-                // that leaves >= 120 workgroups; otherwise 32 rows while that leaves >= 120; otherwise 16.
-                int seg = plan->opt_rbs_seg;
-                const auto wgs = [&](int rows) { return ra.c.tiles_x * (int)rt::cdiv(sc.Ho, rows) * batch; };
-                if (seg <= 0) seg = ((hints & RT_HINT_THROUGHPUT) && wgs(64) >= 120) ? 64 : (wgs(32) >= 120 ? 32 : rt::S3RBSCfg::SEG);
-                seg = seg < 4 ? 4 : (seg > 240 ? 240 : (seg + 3) / 4 * 4);
-                ra.seg = seg;
-                dim3 sgrid((unsigned)(ra.c.tiles_x * (int)rt::cdiv(sc.Ho, seg)), 1u, (unsigned)batch);
-                if (plan->opt_trace) {
-                    if (sc.x_f16) fprintf(stderr, "[rt] conv_f16rbd grid %u x %u x %u seg %d\n", sgrid.x, sgrid.y, sgrid.z, seg);
-                    else fprintf(stderr, "[rt] conv_s3rb%c<%d> grid %u x %u x %u seg %d\n", plan->x_split ? 'd' : 's', plan->y_split ? 1 : 0, sgrid.x,
-                                 sgrid.y, sgrid.z, seg);
-                }
-                if (sc.x_f16) {                         // half2 mode: fp16 tensors, fp16 operands
-                    ra.w1 = plan->rbh_w1_dev; ra.c.w = plan->rbh_w2_dev;
-                    hipLaunchKernelGGL(rt::conv_f16rbd_kernel, sgrid, dim3(512), 0, S(s), ra);
-                    RT_LAUNCH_CHECK("conv_f16rbd_kernel");
-                    continue;
-                }
-                if (plan->x_split) {                    // pre-split input: the DMA-fed block (its own row order of the weight slabs)
-                    ra.w1 = plan->rbd_w1_dev; ra.c.w = plan->rbd_w2_dev;
-                    if (plan->y_split) hipLaunchKernelGGL(rt::conv_s3rbd_kernel<true>, sgrid, dim3(512), 0, S(s), ra);
-                    else hipLaunchKernelGGL(rt::conv_s3rbd_kernel<false>, sgrid, dim3(512), 0, S(s), ra);
-                    RT_LAUNCH_CHECK("conv_s3rbd_kernel");
-                    continue;
-                }
-                if (plan->y_split) hipLaunchKernelGGL(rt::conv_s3rbs_kernel<true>, sgrid, dim3(512), 0, S(s), ra);
-                else hipLaunchKernelGGL(rt::conv_s3rbs_kernel<false>, sgrid, dim3(512), 0, S(s), ra);      // ELU / ELU, as in every tower block
-                RT_LAUNCH_CHECK("conv_s3rbs_kernel");
-                continue;
-            }
-            if (sc.x_f16 || sc.y_f16)
-                return fail(RT_E_UNSUPPORTED, "rt_conv_enqueue: the half2 form of the residual block takes channel-interleaved fp16 tensors only (rt_conv_plan_set_layouts(1, 1, 1))");
-#ifdef RT_EXPERIMENTAL
-            dim3 rgrid((unsigned)(a.tiles_x * tiles_y), 1u, (unsigned)batch);
-            if (plan->opt_trace) fprintf(stderr, "[rt] conv_s3rb x%d y%d grid %u x %u\n", sc.x_il8, sc.y_il8, rgrid.x, rgrid.z);
-            if (sc.x_il8 && sc.y_il8) hipLaunchKernelGGL((rt::conv_s3rb_kernel<true, true>), rgrid, dim3(256), 0, S(s), ra);
-            else if (sc.x_il8) hipLaunchKernelGGL((rt::conv_s3rb_kernel<true, false>), rgrid, dim3(256), 0, S(s), ra);
-            else if (sc.y_il8) hipLaunchKernelGGL((rt::conv_s3rb_kernel<false, true>), rgrid, dim3(256), 0, S(s), ra);
-            else hipLaunchKernelGGL((rt::conv_s3rb_kernel<false, false>), rgrid, dim3(256), 0, S(s), ra);
-            RT_LAUNCH_CHECK("conv_s3rb_kernel");
-            continue;
-#else
-            return fail(RT_E_UNSUPPORTED, "rt_conv_enqueue: this build plans residual blocks for the streaming kernel only (32 -> 32 -> 32 channels, "
-                                           "ELU / ELU, interleaved tensors); the per-tile form is compiled with RT_EXPERIMENTAL");
-#endif
-        }
-        if (sc.s3first) {
-            if (plan->opt_trace) fprintf(stderr, "[rt] conv_s3_first<%d> grid %u x %u x %u twin %d\n", sc.y_il8 ? 1 : 0, grid.x, grid.y, grid.z, a.x2 ? 1 : 0);
-            if (sc.y_il8) hipLaunchKernelGGL((rt::conv_s3_first_kernel<true>), grid, dim3(256), 0, S(s), a);
-            else hipLaunchKernelGGL((rt::conv_s3_first_kernel<false>), grid, dim3(256), 0, S(s), a);
-            RT_LAUNCH_CHECK("conv_s3_first_kernel");
-            continue;
-        }
-        if (sc.split3) {
-            bool launched = false;
-            // split-K for launches that leave SIMDs with a single wave (the low-resolution layers; conv_split.hip.h): KS groups of
-            // 4 waves per workgroup, as many as the CU's 16 wave slots at this kernel's register budget allow.  Chosen from the
-            // per-sample grid so that a sample's result does not depend on the batch it travels in.
-            int ks = 1;
-            const int64_t per_cu = rt::cdiv((int64_t)grid.x * grid.y * (gz / batch), (int64_t)device_cus());
-            // Not with the throughput hint: there other contexts' launches fill the SIMDs, and a 16-wave workgroup with 139 KB of LDS
-            // keeps them off its CU (six one-stream contexts: 2502 against 2589 pairs/s; one context, synchronous: 0.541 against 0.557 ms).
-            if (plan->opt_ksplit > 0 || (plan->opt_ksplit < 0 && !(hints & RT_HINT_THROUGHPUT))) {
-                const int nch = a.CinPad / 16;
-                ks = plan->opt_ksplit > 0 ? plan->opt_ksplit : (per_cu == 1 && nch >= 4 ? 4 : (per_cu <= 2 && nch >= 2 ? 2 : 1));
-            }
-            if (sc.x_f16 || sc.y_f16) {                 // fp16 storage (3-D tensors of half2 mode): planar, 4-row tiles
-                // (the residual's layout is a run-time flag of the kernel: r_il8; an interleaved fp16 OUTPUT exists for fp32 planar input)
-                if (!sc.x_f16 && sc.x_il8 && sc.KH == 3 && sc.KW == 3 && sc.S == 1 && sc.TY == 4 && sc.y_f16) {      // fp32 interleaved in (2-D tower tensor)
-                    if (sc.y_il8) launch_s3<3, 3, 1, true, true, 4, float, _Float16>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);
-                    else launch_s3<3, 3, 1, true, false, 4, float, _Float16>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);
-                    RT_LAUNCH_CHECK("conv_s3_kernel<float, f16>");
-                    continue;
-                }
-                RT_REQUIRE(!sc.x_il8 && !(sc.y_il8 && sc.x_f16) && sc.TY == 4 && sc.y_f16, "rt_conv_enqueue: fp16-storage variant of the split kernel not instantiated");
-#define RT_S3H(kh, kw, st)                                                                                                         \
-    if (!launched && sc.KH == kh && sc.KW == kw && sc.S == st) {                                                                   \
-        if (sc.x_f16) launch_s3<kh, kw, st, false, false, 4, _Float16, _Float16>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace); \
-        else if (sc.y_il8) launch_s3<kh, kw, st, false, true, 4, float, _Float16>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace); \
-        else launch_s3<kh, kw, st, false, false, 4, float, _Float16>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);   \
-        launched = true;                                                                                                           \
-    }
-                RT_S3H(3, 3, 1) RT_S3H(3, 3, 2) RT_S3H(1, 1, 1) RT_S3H(1, 2, 1) RT_S3H(2, 1, 1) RT_S3H(2, 2, 1)
-#undef RT_S3H
-            }
-#ifdef RT_EXPERIMENTAL
-            if (!launched && sc.KH == 3 && sc.KW == 3 && sc.S == 1 && sc.TY == 8) {          // 8-row tiles, 8 waves
-                if (sc.x_il8 && sc.y_il8) launch_s3<3, 3, 1, true, true, 8>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);
-                else if (sc.x_il8) launch_s3<3, 3, 1, true, false, 8>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);
-                else if (sc.y_il8) launch_s3<3, 3, 1, false, true, 8>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);
-                else launch_s3<3, 3, 1, false, false, 8>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);
-                launched = true;
-            }
-#endif
-#define RT_S3(kh, kw, st)                                                                                                   \
-    if (!launched && sc.KH == kh && sc.KW == kw && sc.S == st) {                                                            \
-        if (sc.x_il8 && sc.y_il8) launch_s3<kh, kw, st, true, true>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);        \
-        else if (sc.x_il8) launch_s3<kh, kw, st, true, false>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);              \
-        else if (sc.y_il8) launch_s3<kh, kw, st, false, true>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);              \
-        else launch_s3<kh, kw, st, false, false>(zfold(grid), ks, per_cu, S(s), a, plan->opt_trace);                           \
-        launched = true;                                                                                                    \
-    }
-            RT_S3(3, 3, 1) RT_S3(3, 3, 2) RT_S3(1, 1, 1) RT_S3(1, 2, 1) RT_S3(2, 1, 1) RT_S3(2, 2, 1)
-#undef RT_S3
-            if (!launched) return fail(RT_E_UNSUPPORTED, "conv (split fp16): window %dx%d stride %d not instantiated", sc.KH, sc.KW, sc.S);
-            RT_LAUNCH_CHECK("conv_s3_kernel");
-            continue;
-        }
-        if (sc.f16first) {
-            if (plan->opt_trace) fprintf(stderr, "[rt] conv_f16_first<%d> grid %u x %u x %u twin %d\n", sc.y_il8 ? 1 : 0, grid.x, grid.y, grid.z, a.x2 ? 1 : 0);
-            if (sc.y_il8) hipLaunchKernelGGL((rt::conv_f16_first_kernel<true>), grid, dim3(256), 0, S(s), a, plan->cin);
-            else hipLaunchKernelGGL((rt::conv_f16_first_kernel<false>), grid, dim3(256), 0, S(s), a, plan->cin);
-            RT_LAUNCH_CHECK("conv_f16_first_kernel");
-            continue;
-        }
-        if (sc.f16mma) {
-            // Conv3D 3x3x3 stride 1 between interleaved fp16 tensors: the workgroup walks down the depth axis (conv_f16dw.hip.h)
-            if (plan->c3d_dw && plan->opt_dw != 0 && sc.KH == 3 && sc.KW == 3 && sc.S == 1 && sc.x_il8 && sc.y_il8 && !sc.zs_dev && sc.y_xstride == 1 &&
-                (!plan->has_resid || sc.r_il8) && (plan->act == RT_ACT_NONE || plan->act == RT_ACT_ELU) && !sc.shift_dev) {
-                using Dw = rt::ConvF16DwCfg;
-                const int dw_tiles_x = (int)rt::cdiv(sc.Wo, Dw::TX), dw_nkb = (int)rt::cdiv(sc.Cout, 32);
-                const int64_t npairs = rt::cdiv(dw_tiles_x * (int)rt::cdiv(sc.Ho, Dw::TY), 2);
-                // depth segments: every segment pays two steps' worth of MFMAs for its neighbours' slices and a prologue, every round of
-                // workgroups over the CUs costs a whole segment -- minimise rounds x (segment + overhead); results do not depend on it.
-                // MI355X, NVSmall half2 (profiles/r05_conv3d_layers.txt): batch 8 -- one segment everywhere (conv3D_2 0.206 ms per pair, two
-                // segments 0.215, four 0.228); batch 1 -- conv3D_2 two segments (0.232; one: 0.340), conv3D_4 four (0.137; one: 0.298).
-                int nseg = plan->opt_dw_nseg;
-                double best = 1e30, fill = 1.0;
-                for (int ns = 1; ns <= sc.nz; ns++) {
-                    const int seg = (int)rt::cdiv(sc.nz, ns);
-                    if (ns > 1 && seg < 4) break;
-                    if ((int)rt::cdiv(sc.nz, seg) != ns || (plan->opt_dw_nseg > 0 && ns != std::min(plan->opt_dw_nseg, sc.nz))) continue;
-                    const int64_t wgs = npairs * ns * dw_nkb * batch, rounds = rt::cdiv(wgs, (int64_t)device_cus());
-                    const double steps = seg + (ns > 1 ? 3.0 : 1.7), cost = (double)rounds * steps;
-                    if (cost < best - 1e-9) { best = cost; nseg = ns; fill = (double)wgs / (double)(rounds * device_cus()) * seg / steps; }
-                }
-                // a launch that would leave most of the chip idle or spend its time on segment ends stays with the per-slice kernel (the
-                // 128-channel layers at 12 x 41 x 129: 0.155 against 0.098 ms at batch 1, a tie at batch 8)
-                if (plan->opt_dw < 0 && fill < 0.6) goto dw_declined;
-                nseg = std::max(1, std::min(nseg, sc.nz));
-                a.tiles_x = dw_tiles_x;
-                a.dw_ntiles = a.tiles_x * (int)rt::cdiv(sc.Ho, Dw::TY);
-                a.dw_cpc = plan->c3d_C / 16;
-                a.nb_inner = dw_nkb;
-                a.dw_seg = (int)rt::cdiv(sc.nz, nseg);
-                a.dw_nseg = (int)rt::cdiv(sc.nz, a.dw_seg);
-                const int64_t gx = npairs * a.dw_nseg * a.nb_inner;
-                RT_REQUIRE(gx < (1ll << 31) && batch <= 65535, "rt_conv_enqueue: grid limit exceeded");
-                dim3 gd((unsigned)gx, 1u, (unsigned)batch);
-                const bool resident = a.dw_cpc <= 2, elu = plan->act == RT_ACT_ELU;
-                if (plan->opt_trace)        // conv_f16dw_kernel<resident, has_resid, elu>
-                    fprintf(stderr, "[rt] conv_f16dw<%d,%d,%d> grid %u x %u segments %d x %d slices, %d chunks per slice\n", resident ? 1 : 0,
-                            plan->has_resid ? 1 : 0, elu ? 1 : 0, gd.x, gd.z, a.dw_nseg, a.dw_seg, a.dw_cpc);
-#define RT_DW_LAUNCH(res, hr, el) hipLaunchKernelGGL((rt::conv_f16dw_kernel<res, hr, el>), gd, dim3(512), 0, S(s), a)
-                if (resident) {
-                    if (plan->has_resid) { if (elu) RT_DW_LAUNCH(true, true, true); else RT_DW_LAUNCH(true, true, false); }
-                    else { if (elu) RT_DW_LAUNCH(true, false, true); else RT_DW_LAUNCH(true, false, false); }
-                } else {
-                    if (plan->has_resid) { if (elu) RT_DW_LAUNCH(false, true, true); else RT_DW_LAUNCH(false, true, false); }
-                    else { if (elu) RT_DW_LAUNCH(false, false, true); else RT_DW_LAUNCH(false, false, false); }
-                }
-#undef RT_DW_LAUNCH
-                RT_LAUNCH_CHECK("conv_f16dw_kernel");
-                continue;
-            }
-            dw_declined:
-            // Conv3D between interleaved fp16 tensors: four output rows per wave, operands reused from registers (conv_f16r4.hip.h) -- the
-            // 4 x 32-tile kernel below reads 2 KB of LDS per MFMA and is LDS-bound at 0.3 of the matrix peak on these layers
-            if (sc.KH == 3 && sc.KW == 3 && sc.S == 1 && sc.x_il8 && sc.y_il8 && !sc.zs_dev && sc.TY == 4 && sc.y_xstride == 1 &&
-                (plan->opt_r4 > 0 || (plan->opt_r4 < 0 && plan->is_conv3d && sc.Ho >= 12))) {
-                dim3 g4 = zfold(dim3((unsigned)(a.tiles_x * (int)rt::cdiv(sc.Ho, rt::ConvF16R4Cfg::TY)), grid.y, grid.z));
-                if (plan->opt_trace) fprintf(stderr, "[rt] conv_f16r4 grid %u x %u x %u\n", g4.x, g4.y, g4.z);
-                hipLaunchKernelGGL(rt::conv_f16r4_kernel, g4, dim3(256), 0, S(s), a);
-                RT_LAUNCH_CHECK("conv_f16r4_kernel");
-                continue;
-            }
-            if (plan->opt_trace)        // (after the two walks above: this line names the conv_f16mma_kernel launches below)
-                fprintf(stderr, "[rt] conv_f16mma %dx%d s%d rows %d il8 x%d y%d r%d grid %u x %u x %u\n", sc.KH, sc.KW, sc.S, sc.TY, sc.x_il8,
-                        sc.y_il8, sc.r_il8, grid.x, grid.y, grid.z);
-            if (sc.KH == 3 && sc.KW == 3 && sc.S == 1) {     // the tower layers: tensor layouts x rows per workgroup
-#define RT_F16_331(xi, yi, nw)                                                                                   \
-    if (sc.x_il8 == xi && sc.y_il8 == yi && sc.TY == nw) {                                                       \
-        hipLaunchKernelGGL((rt::conv_f16mma_kernel<3, 3, 1, xi != 0, yi != 0, nw>), zfold(grid), dim3(64 * nw), 0, S(s), a); \
-        RT_LAUNCH_CHECK("conv_f16mma_kernel<3,3,1>");                                                            \
-        continue;                                                                                                \
-    }
-                RT_F16_331(0, 0, 4) RT_F16_331(1, 0, 4) RT_F16_331(0, 1, 4) RT_F16_331(1, 1, 4)
-#undef RT_F16_331
-            }
-            if (sc.KH == 3 && sc.KW == 3 && sc.S == 2 && sc.TY == 4 && (sc.x_il8 || sc.y_il8)) {      // stride-2 Conv3D on interleaved 4-D tensors
-                if (sc.x_il8 && sc.y_il8) hipLaunchKernelGGL((rt::conv_f16mma_kernel<3, 3, 2, true, true>), zfold(grid), dim3(256), 0, S(s), a);
-                else if (sc.x_il8) hipLaunchKernelGGL((rt::conv_f16mma_kernel<3, 3, 2, true, false>), zfold(grid), dim3(256), 0, S(s), a);
-                else hipLaunchKernelGGL((rt::conv_f16mma_kernel<3, 3, 2, false, true>), zfold(grid), dim3(256), 0, S(s), a);
-                RT_LAUNCH_CHECK("conv_f16mma_kernel<3,3,2>");
-                continue;
-            }
-            if (sc.KH == 2 && sc.KW == 2 && sc.S == 1 && sc.TY == 4 && sc.x_il8) {      // phases of a transposed 3-D convolution on interleaved input
-                if (sc.y_il8) hipLaunchKernelGGL((rt::conv_f16mma_kernel<2, 2, 1, true, true>), zfold(grid), dim3(256), 0, S(s), a);
-                else hipLaunchKernelGGL((rt::conv_f16mma_kernel<2, 2, 1, true, false>), zfold(grid), dim3(256), 0, S(s), a);
-                RT_LAUNCH_CHECK("conv_f16mma_kernel<2,2,1,il>");
-                continue;
-            }
-            RT_REQUIRE(!(sc.x_il8 || sc.y_il8 || sc.r_il8) && sc.TY == 4, "rt_conv_enqueue: fp16-arithmetic variant not instantiated");
-#define RT_F16CASE(kh, kw, st)                                                                              \
-    if (sc.KH == kh && sc.KW == kw && sc.S == st) {                                                         \
-        hipLaunchKernelGGL((rt::conv_f16mma_kernel<kh, kw, st>), zfold(grid), dim3(256), 0, S(s), a);              \
-        RT_LAUNCH_CHECK("conv_f16mma_kernel<" #kh "," #kw "," #st ">");                                     \
-        continue;                                                                                           \
-    }
-            RT_F16CASE(3, 3, 2) RT_F16CASE(1, 1, 1) RT_F16CASE(1, 2, 1) RT_F16CASE(2, 1, 1) RT_F16CASE(2, 2, 1)
-#undef RT_F16CASE
-            return fail(RT_E_UNSUPPORTED, "conv (fp16 arithmetic): window %dx%d stride %d not instantiated", sc.KH, sc.KW, sc.S);
-        }
-        if (sc.wino) {
-            RT_REQUIRE(!sc.zs_dev && sc.y_xstride == 1, "rt_conv_enqueue: Winograd kernel takes uniform, x-contiguous slices only");
-            if (sc.x_f16 || sc.y_f16) {
-                RT_REQUIRE(sc.x_f16 && sc.y_f16, "rt_conv_enqueue: the Winograd kernel takes fp16 on both sides or on neither");
-                hipLaunchKernelGGL((rt::conv_wino_f32_kernel<4, _Float16, _Float16>), grid, dim3(256), 0, S(s), a);
-            }
-#ifdef RT_EXPERIMENTAL
-            else if (sc.NW == 8) {
-                RT_REQUIRE(!(sc.x_il8 || sc.y_il8 || sc.r_il8), "rt_conv_enqueue: interleaved tensors need the 4-wave Winograd tile");
-                hipLaunchKernelGGL((rt::conv_wino_f32_kernel<8>), grid, dim3(512), 0, S(s), a);
-            }
-#else
-            else if (sc.NW != 4) return fail(RT_E_UNSUPPORTED, "rt_conv_enqueue: Winograd kernel: 4-wave tile (8 waves: RT_EXPERIMENTAL builds)");
-#endif
-            else if (sc.x_il8 && sc.y_il8) hipLaunchKernelGGL((rt::conv_wino_f32_kernel<4, float, float, true, true>), grid, dim3(256), 0, S(s), a);
-            else if (sc.x_il8) hipLaunchKernelGGL((rt::conv_wino_f32_kernel<4, float, float, true, false>), grid, dim3(256), 0, S(s), a);
-            else if (sc.y_il8) hipLaunchKernelGGL((rt::conv_wino_f32_kernel<4, float, float, false, true>), grid, dim3(256), 0, S(s), a);
-            else if (sc.r_il8) hipLaunchKernelGGL((rt::conv_wino_f32_kernel<4, float, float, false, false, true>), grid, dim3(256), 0, S(s), a);
-            else hipLaunchKernelGGL((rt::conv_wino_f32_kernel<4>), grid, dim3(256), 0, S(s), a);
-            RT_LAUNCH_CHECK("conv_wino_f32_kernel");
-            continue;
-        }
-        if (int rc = launch_sub(sc, a, grid, S(s))) return rc;
-    }
-    return 0;
+    return enqueue_conv(Launch{plan, x, nullptr, 0, y, residual, batch, s, hints}, workspace, workspace_bytes);
 }
 
 extern "C" int rt_has_experimental(void) {
