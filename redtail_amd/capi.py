@@ -393,10 +393,28 @@ class KernelLib:
                                              _ptr(dst_rgb8), 6 * w if dst_step is None else dst_step, batch, stream), "rt_viz_mosaic_u8")
 
     def check_range(self, x, rows, valid, pitch, dtype=RT_F32, limit=65504.0, stream=None):
-        """(max finite |x|, number of elements with |x| >= limit or non-finite) of a device tensor (rt_check_range)"""
+        """(max |x|, number of elements with |x| >= limit or non-finite) over `rows` rows of `valid` leading elements, `pitch` apart, of a
+        device tensor (rt_check_range); max |x| is +inf as soon as one of them is inf or NaN"""
         mx, bad = c_float(), c_int64()
         self.check(self.lib.rt_check_range(_ptr(x), rows, valid, pitch, dtype, limit, ctypes.byref(mx), ctypes.byref(bad), stream), "rt_check_range")
         return mx.value, bad.value
+
+    def convert_format(self, x, y, batch, C, inner, src_kind, dst_kind, stream=None):
+        """(batch, C, inner) tensor between the forms of a plugin boundary (rt_convert_format): kinds 0 fp32 NCHW, 1 fp16 NCHW,
+        2 fp16 NC2HW2 (channel pairs of a pixel in one 4-byte slot, an odd C zero padded)"""
+        self.check(self.lib.rt_convert_format(_ptr(x), _ptr(y), batch, C, inner, src_kind, dst_kind, stream), "rt_convert_format")
+
+    def hash_buffer(self, x, bytes, stream=None):
+        """the 64-bit checksum of `bytes` (a multiple of 4) bytes of a device buffer (rt_hash_buffer), read back to the host"""
+        out, value = c_void_p(), ctypes.c_uint64()
+        self.check(self.lib.rt_malloc(ctypes.byref(out), 8), "rt_malloc")
+        try:
+            self.check(self.lib.rt_hash_buffer(_ptr(x), bytes, out, stream), "rt_hash_buffer")
+            self.check(self.lib.rt_memcpy_d2h(ctypes.byref(value), out, 8, stream), "rt_memcpy_d2h")
+            self.check(self.lib.rt_stream_sync(stream), "rt_stream_sync")
+        finally:
+            self.lib.rt_free(out)
+        return value.value
 
     def conv2d_plan(self, w_host, b_host, Cin, Cout, Hin, Win, k, stride, pad, act=0, has_residual=False,
                     dtype=RT_F32, transposed=False, flags=0):
