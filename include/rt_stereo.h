@@ -221,6 +221,33 @@ enum { RT_DISP_NET = 0, RT_DISP_PIXELS_F32 = 1, RT_DISP_KITTI_U16 = 2 };
 int rt_lr_consistency(const void* net_disp, int batch, int H, int W, float scale, float max_diff_px, void* out, int out_kind,
                       void* mask_u8, void* right_out, void* valid_count, rtStream stream);
 
+/* ---- speckle filter (no counterpart in the reference; stereo_image_proc's speckle_size / speckle_range, cv::filterSpeckles) ------------ */
+/* Removes small connected blobs of a disparity map: what the left-right check leaves inside its holes and along depth edges, and what
+ * rt_disparity_to_points would turn into clusters of points floating in space.  Its place is network geometry, between rt_lr_consistency
+ * (or rt_disparity_scale) and rt_disparity_to_frame / rt_disparity_to_points, whose "do not mix with invalid taps" rule then sees the
+ * removed pixels.
+ * disp_px:  (batch,1,H,W) fp32      mask_u8: (batch,1,H,W) the 255 / 0 mask of rt_lr_consistency, or NULL
+ * A pixel is LIVE iff (mask_u8 == NULL || mask != 0) && d == d: a NaN is never live; an infinity is live but adjacent to nothing.
+ * Two live pixels of the same image are ADJACENT iff they are 4-neighbours (left / right in a row, up / down in a column) and
+ *   fabsf(d(p) - d(q)) <= max_diff_px     in fp32, the difference and the comparison each rounded on its own
+ * (-0.f and 0.f are adjacent at max_diff_px = 0).  Nothing wraps from the end of a row to the next row, nothing joins image n to image
+ * n + 1.  COMPONENTS are the classes of the transitive closure of adjacency -- cv::filterSpeckles' neighbour-to-neighbour region growing:
+ * a ramp of small steps is one component whatever its end-to-end range.  A component is a SPECKLE iff it has <= max_size pixels
+ * (OpenCV's rule: larger blobs are not affected).  keep(p) = live and not in a speckle, and
+ *   out[p]         = keep ? disp_px[p] : 0.f      (the bits are copied, nothing is recomputed)
+ *   out_mask_u8[p] = keep ? 255 : 0               uint8, may be NULL
+ *   valid_count[n] = kept pixels of image n       `batch` uint64 on the device, zeroed by the entry, may be NULL
+ * max_size == 0 is legal and removes nothing: mask = live, value or 0.  out == disp_px and out_mask_u8 == mask_u8 are legal (in place,
+ * bit-identical to the out-of-place call); no other overlap is.  The result is a pure function of the inputs -- which pixels go depends
+ * only on integer component sizes -- so every run is bit-identical, in whatever order the device ran the work.
+ * `workspace`: device memory of rt_speckle_workspace_bytes(batch, H, W) bytes (one label and one size word per pixel), 4-byte aligned,
+ * private to the stream until the launches have run: four of them (tiles, tile borders, sizes, apply), one when max_size == 0.
+ * Errors, found before anything is written: a null disp_px or out; batch, H or W < 1; H * W >= 2^31 or batch > 32767; max_size < 0;
+ * max_diff_px negative, NaN or infinite; a missing or short workspace.  rt_speckle_workspace_bytes returns 0 for sizes the op refuses. */
+size_t rt_speckle_workspace_bytes(int batch, int H, int W);
+int rt_disparity_speckle(const void* disp_px, const void* mask_u8, int batch, int H, int W, int max_size, float max_diff_px,
+                         void* out, void* out_mask_u8, void* valid_count, void* workspace, size_t workspace_bytes, rtStream stream);
+
 /* ---- frames of any size in, disparity at the frame's size out ------------------------------------------------------------------ */
 /* The whole of cv::resize(INTER_AREA) on the fp32 image as the ROS node calls it for whatever the camera sends
  * (stereo_dnn_ros_node.cpp:42-58), for both frames of a pair batch in one launch.  Arguments as rt_preprocess_frames_u8.

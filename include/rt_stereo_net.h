@@ -186,6 +186,29 @@ typedef struct rtRectifyCall {
 int rt_net_execute_frames_raw(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out /* or NULL */, const rtRectifyCall* rect,
                               rtStream stream);
 
+/* The calls above with a speckle filter (rt_stereo.h: rt_disparity_speckle, where live pixels, adjacency, components and what is written
+ * are defined; stereo_image_proc's speckle_size / speckle_range) where it belongs: in network geometry, in front of the resampling.
+ *   speckle == NULL: rt_net_execute_frames_raw on the same arguments; with rect == NULL rt_net_execute_frames_3d, with out == NULL as well
+ *                    rt_net_execute_frames_ex; refusals included.
+ *   speckle != NULL: call->geometry must be RT_GEOM_FRAME (RT_GEOM_NET: RT_E_UNSUPPORTED, as for depth).  The sequence is the existing one
+ *                    with ONE rt_disparity_speckle(max_size, max_diff_px) between the step that makes network-geometry pixels and
+ *                    rt_disparity_to_frame / rt_disparity_to_points: behind rt_lr_consistency in place on the net-owned disparity and mask;
+ *                    without a check with a NULL input mask into those two buffers -- behind rt_disparity_scale in place, for the 3-D
+ *                    models (whose output is pixels already) out of place from the engine's output.  The back end therefore always gets
+ *                    a mask, and call->mask_u8 / call->valid_count are legal without a check: they then say which pixels the filter kept.
+ * Composition is the definition: every output is bit-identical to those op-level calls made by hand around rt_net_execute.  The filter
+ * costs launches and no engine work.  Its workspace is a buffer the net owns, made on first use for max_batch.  It runs outside the
+ * engine's graph, so every pointer may rotate in graph mode; stream == NULL: synchronous.  All checks of all four structs are made before
+ * the first launch, so an error writes nothing: whatever the wrapped calls refuse (mask_u8 / valid_count with neither a check nor a filter
+ * included), a wrong struct_bytes, max_size < 0, a max_diff_px that is negative, NaN or infinite. */
+typedef struct rtSpeckleCall {
+    size_t struct_bytes;       /* sizeof(rtSpeckleCall) */
+    int max_size;              /* components of at most this many network-geometry pixels are removed (speckle_size); 0 removes nothing */
+    float max_diff_px;         /* largest step between neighbours of one component, network-geometry pixels (speckle_range) */
+} rtSpeckleCall;
+int rt_net_execute_frames_filtered(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out /* or NULL */,
+                                   const rtRectifyCall* rect /* or NULL */, const rtSpeckleCall* speckle /* or NULL */, rtStream stream);
+
 /* Per-launch timing through nvinfer1::IProfiler (single stream, one event pair per launch):
  * writes "name<TAB>milliseconds\n" lines into buf.  Returns 0 or an error. */
 int rt_net_profile(rtStereoNet* net, const void* left, const void* right, void* disp, int batch, char* buf,

@@ -131,6 +131,9 @@ KERNEL_SYMBOLS = {
     "rt_disparity_to_points": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(StereoCamera), c_float, c_float, c_void_p,
                                        c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_size_t, c_void_p]),
+    "rt_speckle_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "rt_disparity_speckle": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                     c_void_p]),
     "rt_rectify_camera_from_info": (c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), POINTER(c_double),
                                             POINTER(RectifyCamera)]),
     "rt_rectify_frames_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, POINTER(RectifyCamera), POINTER(RectifyCamera), c_void_p,
@@ -329,6 +332,21 @@ class KernelLib:
                                                    color_step, encoding, _ptr(disp_out), disp_kind, _ptr(out_mask), _ptr(valid_count), _ptr(depth),
                                                    depth_kind, _ptr(points), _ptr(points_compact), _ptr(count), _ptr(workspace), workspace_bytes,
                                                    stream), "rt_disparity_to_points")
+
+    def speckle_workspace_bytes(self, batch, h, w):
+        """bytes of device workspace disparity_speckle needs (0 for sizes it refuses)"""
+        return self.lib.rt_speckle_workspace_bytes(batch, h, w)
+
+    def disparity_speckle(self, disp_px, batch, h, w, max_size, max_diff_px, out, mask=None, out_mask=None, valid_count=None, workspace=None,
+                          workspace_bytes=None, stream=None):
+        """the speckle filter (stereo_image_proc's speckle_size / speckle_range, cv::filterSpeckles) on a (N,1,h,w) fp32 disparity (+ the
+        255 / 0 mask of lr_consistency): 4-connected components of live pixels whose neighbours differ by <= max_diff_px; those of at most
+        max_size pixels become 0 in out and in out_mask.  In place (out = disp_px, out_mask = mask) is legal.  valid_count: N uint64 on the
+        device; workspace: speckle_workspace_bytes of device memory."""
+        if workspace_bytes is None:
+            workspace_bytes = 0 if workspace is None else (workspace.numel() * workspace.element_size() if hasattr(workspace, "numel") else workspace.nbytes)
+        self.check(self.lib.rt_disparity_speckle(_ptr(disp_px), _ptr(mask), batch, h, w, max_size, max_diff_px, _ptr(out), _ptr(out_mask),
+                                                 _ptr(valid_count), _ptr(workspace), workspace_bytes, stream), "rt_disparity_speckle")
 
     def corr_softargmax_pitched(self, l, r, out, batch, C, H, W, D, is_min, in_pitch, out_pitch, out_bstride=0,
                                 dtype=RT_F32, stream=None):
@@ -541,6 +559,7 @@ NET_SYMBOLS = {
     "rt_net_execute_frames_ex": (c_int, [c_void_p, c_void_p, c_void_p]),
     "rt_net_execute_frames_3d": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "rt_net_execute_frames_raw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rt_net_execute_frames_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rt_net_profile": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_char_p, c_size_t]),
     "rt_net_num_layers": (c_int, [c_void_p]),
     "rt_net_num_launches": (c_int, [c_void_p]),
@@ -583,6 +602,11 @@ class RectifyCall(ctypes.Structure):
     """rtRectifyCall (include/rt_stereo_net.h)"""
     _fields_ = [("struct_bytes", c_size_t), ("left", RectifyCamera), ("right", RectifyCamera), ("left_rect_u8", c_void_p),
                 ("right_rect_u8", c_void_p), ("rect_step", c_int64)]
+
+
+class SpeckleCall(ctypes.Structure):
+    """rtSpeckleCall (include/rt_stereo_net.h)"""
+    _fields_ = [("struct_bytes", c_size_t), ("max_size", c_int), ("max_diff_px", c_float)]
 
 
 def pack_weights(weights, fp16=False):
@@ -819,6 +843,37 @@ class StereoNet:
                            _ptr(left_rect), _ptr(right_rect), rect_step)
         self.netlib.check(self.netlib.lib.rt_net_execute_frames_raw(self.handle, ctypes.byref(call), out, ctypes.byref(rect), stream),
                           "rt_net_execute_frames_raw")
+
+    def execute_frames_filtered(self, left_u8, right_u8, encoding, speckle_size=None, speckle_range=1.0, rect_left=None, rect_right=None,
+                                camera=None, disp=None, kind=RT_DISP_PIXELS_F32, geometry=RT_GEOM_FRAME, resize=RT_RESIZE_CV_AREA,
+                                max_diff_px=-1.0, mask=None, valid_count=None, min_depth=0.0, max_depth=float("inf"), depth=None,
+                                depth_kind=RT_DEPTH_M_F32, points=None, points_compact=None, count=None, batch=1, stream=None, src_step=None,
+                                src_w=None, struct_bytes=None, depth_struct_bytes=None, no_depth_call=False, left_rect=None, right_rect=None,
+                                rect_step=None, rect_struct_bytes=None, speckle_struct_bytes=None):
+        """rt_net_execute_frames_filtered: execute_frames_raw (rect_left / rect_right given), execute_frames_3d or (no_depth_call)
+        execute_frames_ex with the same keywords, plus one disparity_speckle(speckle_size, speckle_range) in network geometry in front of
+        the resampling; mask and valid_count are then legal without a check.  speckle_size=None: no filter, the wrapped call itself."""
+        h, w, step = self._frame_geometry("rt_net_execute_frames_filtered", left_u8, right_u8, encoding, batch, src_step, src_w)
+        call = FrameCall(ctypes.sizeof(FrameCall) if struct_bytes is None else struct_bytes, _ptr(left_u8), _ptr(right_u8), h, w, step, encoding,
+                         resize, _ptr(disp), kind, geometry, max_diff_px, _ptr(mask), _ptr(valid_count), batch)
+        out = None
+        if not no_depth_call:
+            out = ctypes.byref(DepthCall(ctypes.sizeof(DepthCall) if depth_struct_bytes is None else depth_struct_bytes,
+                                         camera if camera is not None else StereoCamera(), min_depth, max_depth, _ptr(depth), depth_kind,
+                                         _ptr(points), _ptr(points_compact), _ptr(count)))
+        rect = None
+        if rect_left is not None or rect_right is not None:
+            if rect_step is None:
+                given = left_rect if left_rect is not None else right_rect
+                rect_step = 0 if given is None else (given.stride(1) if hasattr(given, "data_ptr") else given.strides[1])
+            rect = ctypes.byref(RectifyCall(ctypes.sizeof(RectifyCall) if rect_struct_bytes is None else rect_struct_bytes, rect_left, rect_right,
+                                            _ptr(left_rect), _ptr(right_rect), rect_step))
+        speckle = None
+        if speckle_size is not None:
+            speckle = ctypes.byref(SpeckleCall(ctypes.sizeof(SpeckleCall) if speckle_struct_bytes is None else speckle_struct_bytes, speckle_size,
+                                               speckle_range))
+        self.netlib.check(self.netlib.lib.rt_net_execute_frames_filtered(self.handle, ctypes.byref(call), out, rect, speckle, stream),
+                          "rt_net_execute_frames_filtered")
 
     def set_debug(self, on=True):
         """IExecutionContext::setDebugSync: synchronise every launch and range-check the input of every fp16-pipe convolution"""

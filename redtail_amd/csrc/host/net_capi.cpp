@@ -69,6 +69,8 @@ struct rtStereoNet {
     size_t points_ws_bytes = 0;
     void* rect[2] = {nullptr, nullptr};           // rt_net_execute_frames_raw: dense rectified frames for max_batch, grown on demand
     size_t rect_bytes = 0;
+    void* speckle_ws = nullptr;                   // rt_net_execute_frames_filtered: rt_disparity_speckle's workspace for max_batch, made on first use
+    size_t speckle_ws_bytes = 0;
     ~rtStereoNet() {
         if (context) context->destroy();
         if (engine) engine->destroy();
@@ -80,6 +82,7 @@ struct rtStereoNet {
         rt_free(points_ws);
         rt_free(rect[0]);
         rt_free(rect[1]);
+        rt_free(speckle_ws);
     }
 };
 
@@ -401,9 +404,11 @@ extern "C" int rt_net_execute_frames_viz(rtStereoNet* net, const void* left_u8, 
 // end's, and its other arguments are checked here.
 // d != NULL: rt_net_execute_frames_3d -- frame geometry only, rt_disparity_to_points behind the network, c->disp optional
 // r != NULL: rt_net_execute_frames_raw -- c's frames are raw; one rt_rectify_frames_u8 launch in front, everything else on its output
+// sp != NULL: rt_net_execute_frames_filtered -- frame geometry only, one rt_disparity_speckle between the step that makes network-geometry
+//            pixels and the back end, which then always gets a mask
 namespace {
 int execute_frames_ex(const std::string& fn, rtStereoNet* net, const rtFrameCall* c, const rtDepthCall* d, const rtRectifyCall* r,
-                      rtStream stream) {
+                      const rtSpeckleCall* sp, rtStream stream) {
     if (!net || !net->context || !c) return fail(fn + "null pointer");
     if (r && r->struct_bytes != sizeof(rtRectifyCall))
         return fail(fn + "struct_bytes " + std::to_string(r->struct_bytes) + " is not sizeof(rtRectifyCall) = " + std::to_string(sizeof(rtRectifyCall)));
@@ -411,6 +416,8 @@ int execute_frames_ex(const std::string& fn, rtStereoNet* net, const rtFrameCall
         return fail(fn + "struct_bytes " + std::to_string(c->struct_bytes) + " is not sizeof(rtFrameCall) = " + std::to_string(sizeof(rtFrameCall)));
     if (d && d->struct_bytes != sizeof(rtDepthCall))
         return fail(fn + "struct_bytes " + std::to_string(d->struct_bytes) + " is not sizeof(rtDepthCall) = " + std::to_string(sizeof(rtDepthCall)));
+    if (sp && sp->struct_bytes != sizeof(rtSpeckleCall))
+        return fail(fn + "struct_bytes " + std::to_string(sp->struct_bytes) + " is not sizeof(rtSpeckleCall) = " + std::to_string(sizeof(rtSpeckleCall)));
     if (!c->left_u8 || !c->right_u8 || (!d && !c->disp)) return fail(fn + "null pointer");
     if (c->resize != RT_RESIZE_AREA_DOWN && c->resize != RT_RESIZE_CV_AREA) return fail(fn + "unknown resize " + std::to_string(c->resize));
     if (c->geometry != RT_GEOM_NET && c->geometry != RT_GEOM_FRAME) return fail(fn + "unknown geometry " + std::to_string(c->geometry));
@@ -435,10 +442,18 @@ int execute_frames_ex(const std::string& fn, rtStereoNet* net, const rtFrameCall
         if (((reinterpret_cast<uintptr_t>(d->points) | reinterpret_cast<uintptr_t>(d->points_compact)) & 15) != 0)
             return fail(fn + "a cloud must start on a 16-byte boundary");
     }
+    if (sp) {                                          // what only rt_disparity_speckle can refuse
+        if (c->geometry != RT_GEOM_FRAME) {
+            fail(fn + "the speckle filter runs in front of the resampling to the frame: RT_GEOM_NET is not supported, use RT_GEOM_FRAME");
+            return RT_E_UNSUPPORTED;
+        }
+        if (sp->max_size < 0) return fail(fn + "speckle max_size must be >= 0");
+        if (!(sp->max_diff_px >= 0.f && sp->max_diff_px <= 3.402823466e38f)) return fail(fn + "speckle max_diff_px must be a finite number >= 0");
+    }
     if (c->encoding < RT_ENC_BGR8 || c->encoding > RT_ENC_RGBA8) return fail(fn + "unknown encoding " + std::to_string(c->encoding));
     if (c->max_diff_px != c->max_diff_px) return fail(fn + "max_diff_px is not a number");
     const bool check = c->max_diff_px >= 0.f;
-    if (!check && (c->mask_u8 || c->valid_count)) return fail(fn + "mask_u8 and valid_count need a check (max_diff_px >= 0)");
+    if (!check && !sp && (c->mask_u8 || c->valid_count)) return fail(fn + "mask_u8 and valid_count need a check (max_diff_px >= 0)");
     const int batch = c->batch, engine_batch = check ? 2 * batch : batch;
     if (batch < 1 || (int64_t)(check ? 2 : 1) * batch > net->max_batch)
         return fail(fn + "batch " + std::to_string(batch) + (check ? " with a check" : "") + " needs an engine batch of " +
@@ -527,6 +542,12 @@ int execute_frames_ex(const std::string& fn, rtStereoNet* net, const rtFrameCall
             net->points_ws_bytes = need;
         }
     }
+    if (sp && !net->speckle_ws) {
+        const size_t need = rt_speckle_workspace_bytes(net->max_batch, H, W);
+        if (need == 0) return fail(fn + "the network's size is beyond the speckle filter's limits");
+        if (rt_malloc(&net->speckle_ws, need) != 0) return fail(fn + rt_last_error_string());
+        net->speckle_ws_bytes = need;
+    }
     int rc;
     if (c->resize == RT_RESIZE_CV_AREA)
         rc = rt_preprocess_frames_u8_cv(c->left_u8, c->right_u8, c->src_h, c->src_w, c->src_step, c->encoding, net->frame_in[0], net->frame_in[1], H,
@@ -540,8 +561,13 @@ int execute_frames_ex(const std::string& fn, rtStereoNet* net, const rtFrameCall
     if (!ok) return fail(fn + net->log.last_error);
     const float scale = net->model == RT_MODEL_RESNET18_2D ? (float)W : 1.f;            // as rt_net_execute_frames
     const int64_t n = batch * pixels;
-    if (d) {                                           // the frame-geometry sequence below with rt_disparity_to_points as its last step
-        const void* px = net->frame_disp;
+    if (!frame) {                                      // (never with d or sp: both are frame geometry only)
+        if (check) rc = rt_lr_consistency(net->frame_disp, batch, H, W, scale, c->max_diff_px, c->disp, c->disp_kind, c->mask_u8, nullptr, c->valid_count, stream);
+        else if (c->disp_kind == RT_DISP_NET) rc = rt_memcpy_d2d(c->disp, net->frame_disp, (size_t)n * sizeof(float), stream);
+        else if (c->disp_kind == RT_DISP_PIXELS_F32) rc = rt_disparity_scale(net->frame_disp, c->disp, n, scale, stream);
+        else rc = rt_disparity_to_u16(net->frame_disp, c->disp, n, 256.f * scale, stream);
+    } else {
+        const void* px = net->frame_disp;              // the 3-D models' output is in pixels already
         const void* mask = nullptr;
         if (check) {
             rc = rt_lr_consistency(net->frame_disp, batch, H, W, scale, c->max_diff_px, net->frame_px, RT_DISP_PIXELS_F32, net->frame_mask, nullptr, nullptr, stream);
@@ -551,26 +577,19 @@ int execute_frames_ex(const std::string& fn, rtStereoNet* net, const rtFrameCall
             rc = rt_disparity_scale(net->frame_disp, net->frame_px, n, scale, stream);
             px = net->frame_px;
         }
-        if (rc == 0)
+        if (rc == 0 && sp) {                           // in place on frame_px / frame_mask, or out of place from frame_disp where no step ran
+            rc = rt_disparity_speckle(px, mask, batch, H, W, sp->max_size, sp->max_diff_px, net->frame_px, net->frame_mask, nullptr, net->speckle_ws,
+                                      net->speckle_ws_bytes, stream);
+            px = net->frame_px;
+            mask = net->frame_mask;
+        }
+        // (without a mask c->mask_u8 and c->valid_count are NULL: checked above)
+        if (rc == 0 && d)                              // rt_disparity_to_points in the place of rt_disparity_to_frame
             rc = rt_disparity_to_points(px, mask, batch, H, W, c->src_h, c->src_w, &d->camera, d->min_depth, d->max_depth, c->left_u8, c->src_step,
                                         c->encoding, c->disp, c->disp_kind, c->mask_u8, c->valid_count, d->depth, d->depth_kind, d->points,
                                         d->points_compact, d->count, net->points_ws, net->points_ws_bytes, stream);
-    } else if (!frame) {
-        if (check) rc = rt_lr_consistency(net->frame_disp, batch, H, W, scale, c->max_diff_px, c->disp, c->disp_kind, c->mask_u8, nullptr, c->valid_count, stream);
-        else if (c->disp_kind == RT_DISP_NET) rc = rt_memcpy_d2d(c->disp, net->frame_disp, (size_t)n * sizeof(float), stream);
-        else if (c->disp_kind == RT_DISP_PIXELS_F32) rc = rt_disparity_scale(net->frame_disp, c->disp, n, scale, stream);
-        else rc = rt_disparity_to_u16(net->frame_disp, c->disp, n, 256.f * scale, stream);
-    } else if (check) {
-        rc = rt_lr_consistency(net->frame_disp, batch, H, W, scale, c->max_diff_px, net->frame_px, RT_DISP_PIXELS_F32, net->frame_mask, nullptr, nullptr, stream);
-        if (rc == 0)
-            rc = rt_disparity_to_frame(net->frame_px, net->frame_mask, batch, H, W, c->disp, c->disp_kind, c->src_h, c->src_w, c->mask_u8, c->valid_count, stream);
-    } else {
-        const void* px = net->frame_disp;              // the 3-D models' output is in pixels already
-        if (net->model == RT_MODEL_RESNET18_2D) {
-            rc = rt_disparity_scale(net->frame_disp, net->frame_px, n, scale, stream);
-            px = net->frame_px;
-        }
-        if (rc == 0) rc = rt_disparity_to_frame(px, nullptr, batch, H, W, c->disp, c->disp_kind, c->src_h, c->src_w, nullptr, nullptr, stream);
+        else if (rc == 0)
+            rc = rt_disparity_to_frame(px, mask, batch, H, W, c->disp, c->disp_kind, c->src_h, c->src_w, c->mask_u8, c->valid_count, stream);
     }
     if (rc == 0 && !stream) rc = rt_stream_sync(nullptr);
     if (rc != 0) return fail(fn + rt_last_error_string());
@@ -579,21 +598,28 @@ int execute_frames_ex(const std::string& fn, rtStereoNet* net, const rtFrameCall
 }  // namespace
 
 extern "C" int rt_net_execute_frames_ex(rtStereoNet* net, const rtFrameCall* call, rtStream stream) {
-    return execute_frames_ex("rt_net_execute_frames_ex: ", net, call, nullptr, nullptr, stream);
+    return execute_frames_ex("rt_net_execute_frames_ex: ", net, call, nullptr, nullptr, nullptr, stream);
 }
 
 // rt_net_execute_frames_ex in frame geometry with depth and / or a point cloud beside (or instead of) the disparity: the same launches,
 // rt_disparity_to_points in the place of rt_disparity_to_frame
 extern "C" int rt_net_execute_frames_3d(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out, rtStream stream) {
-    if (!out) return execute_frames_ex("rt_net_execute_frames_ex: ", net, call, nullptr, nullptr, stream);
-    return execute_frames_ex("rt_net_execute_frames_3d: ", net, call, out, nullptr, stream);
+    if (!out) return execute_frames_ex("rt_net_execute_frames_ex: ", net, call, nullptr, nullptr, nullptr, stream);
+    return execute_frames_ex("rt_net_execute_frames_3d: ", net, call, out, nullptr, nullptr, stream);
 }
 
 // raw frames in: one rt_rectify_frames_u8 launch, then the call above on its output
 extern "C" int rt_net_execute_frames_raw(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out, const rtRectifyCall* rect,
                                          rtStream stream) {
     if (!rect) return fail("rt_net_execute_frames_raw: null pointer");
-    return execute_frames_ex("rt_net_execute_frames_raw: ", net, call, out, rect, stream);
+    return execute_frames_ex("rt_net_execute_frames_raw: ", net, call, out, rect, nullptr, stream);
+}
+
+// the same with a speckle filter in network geometry, in front of the resampling; without one, the call above (rect), or the ones above it
+extern "C" int rt_net_execute_frames_filtered(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out, const rtRectifyCall* rect,
+                                              const rtSpeckleCall* speckle, rtStream stream) {
+    if (!speckle) return rect ? rt_net_execute_frames_raw(net, call, out, rect, stream) : rt_net_execute_frames_3d(net, call, out, stream);
+    return execute_frames_ex("rt_net_execute_frames_filtered: ", net, call, out, rect, speckle, stream);
 }
 
 extern "C" int rt_net_profile(rtStereoNet* net, const void* left, const void* right, void* disp, int batch, char* buf,

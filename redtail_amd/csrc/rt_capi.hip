@@ -29,6 +29,7 @@
 #include "kernels/deconv3d_small.hip.h"
 #include "kernels/imgproc.hip.h"
 #include "kernels/rectify.hip.h"
+#include "kernels/speckle.hip.h"
 #include "kernels/conv_f16.hip.h"
 #include "kernels/conv_f16_first.hip.h"
 #include "kernels/conv_f16r4.hip.h"
@@ -970,6 +971,55 @@ extern "C" int rt_lr_consistency(const void* net_disp, int batch, int H, int W, 
     else if (out_kind == RT_DISP_PIXELS_F32) launch(rt::lr_consistency_kernel<1>);
     else launch(rt::lr_consistency_kernel<2>);
     RT_LAUNCH_CHECK("lr_consistency_kernel");
+    return 0;
+}
+
+// speckle filter of a network-geometry disparity (speckle.hip.h): tiles in LDS, tile borders, sizes, apply -- four launches, one with
+// max_size == 0, where nothing can be a speckle.  The workspace holds one label and one size word per pixel.
+extern "C" size_t rt_speckle_workspace_bytes(int batch, int H, int W) {
+    if (batch < 1 || batch > 32767 || H < 1 || W < 1 || (int64_t)H * W >= ((int64_t)1 << 31)) return 0;
+    return (size_t)batch * (size_t)H * (size_t)W * 2 * sizeof(unsigned);
+}
+
+extern "C" int rt_disparity_speckle(const void* disp_px, const void* mask_u8, int batch, int H, int W, int max_size, float max_diff_px, void* out,
+                                    void* out_mask_u8, void* valid_count, void* workspace, size_t workspace_bytes, rtStream s) {
+    const char* fn = "rt_disparity_speckle";
+    RT_REQUIRE(disp_px && out, "%s: null pointer", fn);
+    RT_REQUIRE(batch >= 1 && batch <= 32767 && H >= 1 && W >= 1 && (int64_t)H * W < ((int64_t)1 << 31), "%s: bad dims", fn);
+    RT_REQUIRE(max_size >= 0, "%s: max_size must be >= 0", fn);
+    RT_REQUIRE(max_diff_px >= 0.f && max_diff_px <= 3.402823466e38f, "%s: max_diff_px must be a finite number >= 0", fn);       // (false for NaN too)
+    const size_t need = rt_speckle_workspace_bytes(batch, H, W);
+    RT_REQUIRE(workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 3) == 0,
+               "%s: workspace of %zu bytes, rt_speckle_workspace_bytes asks for %zu (4-byte aligned)", fn, workspace ? workspace_bytes : (size_t)0, need);
+    if (valid_count) RT_HIP(hipMemsetAsync(valid_count, 0, (size_t)batch * sizeof(unsigned long long), S(s)));
+    const float* d = static_cast<const float*>(disp_px);
+    const unsigned char* m = static_cast<const unsigned char*>(mask_u8);
+    const int64_t plane = (int64_t)H * W;
+    unsigned* label = static_cast<unsigned*>(workspace);
+    unsigned* size = label + (size_t)batch * plane;
+    const dim3 flat((unsigned)rt::cdiv(plane, 256), (unsigned)batch);
+    if (max_size > 0) {
+        const int64_t tx = rt::cdiv(W, rt::kSpeckleTile), ty = rt::cdiv(H, rt::kSpeckleTile);
+        hipLaunchKernelGGL(rt::speckle_tile_kernel, dim3((unsigned)(tx * ty), (unsigned)batch), dim3(256), 0, S(s), d, m, H, W, (int)tx, max_diff_px,
+                           label, size);
+        RT_LAUNCH_CHECK("speckle_tile_kernel");
+        const int64_t nv = (tx - 1) * H, items = nv + (ty - 1) * W;
+        if (items > 0) {
+            hipLaunchKernelGGL(rt::speckle_border_kernel, dim3((unsigned)rt::cdiv(items, 256), (unsigned)batch), dim3(256), 0, S(s), d, m, H, W, nv,
+                               items, max_diff_px, label);
+            RT_LAUNCH_CHECK("speckle_border_kernel");
+            hipLaunchKernelGGL(rt::speckle_size_kernel, flat, dim3(256), 0, S(s), static_cast<const unsigned*>(label), size, plane);
+            RT_LAUNCH_CHECK("speckle_size_kernel");
+        }
+        hipLaunchKernelGGL(rt::speckle_apply_kernel<true>, flat, dim3(256), 0, S(s), d, m, plane, (unsigned)max_size,
+                           static_cast<const unsigned*>(label), static_cast<const unsigned*>(size), static_cast<float*>(out),
+                           static_cast<unsigned char*>(out_mask_u8), static_cast<unsigned long long*>(valid_count));
+    } else {
+        hipLaunchKernelGGL(rt::speckle_apply_kernel<false>, flat, dim3(256), 0, S(s), d, m, plane, 0u, static_cast<const unsigned*>(label),
+                           static_cast<const unsigned*>(size), static_cast<float*>(out), static_cast<unsigned char*>(out_mask_u8),
+                           static_cast<unsigned long long*>(valid_count));
+    }
+    RT_LAUNCH_CHECK("speckle_apply_kernel");
     return 0;
 }
 

@@ -144,3 +144,34 @@ def synth_disparity(h, w):
         d = field(xx - d)
     xr = xx - d
     return np.where((xr >= 0) & (xr <= w - 1), d, 0.0).astype(np.float32)
+
+
+def synth_speckle_disparity(n, h, w, seed=11):
+    """A checked disparity as the left-right check leaves it, for the speckle filter's timing and full-size test: synth_pair's smooth field
+    with a dozen nearer rectangles per image; holes where the check fails -- the out-of-view band on the left, an occlusion band as wide
+    as the disparity jump on the left of every rectangle, 1 % pinholes -- and, inside the holes, 3 % surviving pixels grown into small
+    islands with wrong values (the speckles).  Returns (px (n,1,h,w) float32 pixels, 0 where invalid; mask (n,1,h,w) uint8 255 / 0)."""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    s = w / 1257.0
+    px = np.zeros((n, 1, h, w), np.float32)
+    mask = np.zeros((n, 1, h, w), np.uint8)
+    for i in range(n):
+        d = ((4 + 60 * (yy / h) + 8 * np.sin(2 * np.pi * xx / w)) * s).astype(np.float32)
+        valid = xx >= d                                   # the match of a pixel left of its disparity lies outside the right image
+        for _ in range(12):
+            hh, ww = int(rng.integers(max(2, h // 12), max(3, h // 3))), int(rng.integers(max(2, w // 20), max(3, w // 5)))
+            y0, x0 = int(rng.integers(0, max(1, h - hh))), int(rng.integers(0, max(1, w - ww)))
+            jump = np.float32(rng.uniform(8, 40) * s)
+            d[y0:y0 + hh, x0:x0 + ww] += jump
+            valid[y0:y0 + hh, max(0, x0 - int(jump)):x0] = False
+        seeds = ~valid & (rng.uniform(size=(h, w)) < 0.03)
+        islands = seeds.copy()
+        islands[:, 1:] |= seeds[:, :-1] & (rng.uniform(size=(h, w - 1)) < 0.5)
+        islands[1:, :] |= islands[:-1, :] & (rng.uniform(size=(h - 1, w)) < 0.3)
+        islands &= ~valid
+        d = np.where(islands, d + rng.normal(0, 5, (h, w)).astype(np.float32), d).astype(np.float32)
+        valid = (valid | islands) & (rng.uniform(size=(h, w)) >= 0.01)
+        px[i, 0] = np.where(valid, d, np.float32(0))
+        mask[i, 0] = np.where(valid, 255, 0)
+    return px, mask
