@@ -50,6 +50,27 @@ int fail(const std::string& msg) {
     return RT_E_BADARG;
 }
 
+// Device memory a net owns: freed with it, never copied.
+struct DeviceBuffer {
+    void* p = nullptr;
+    size_t bytes = 0;
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer&) = delete;
+    DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+    ~DeviceBuffer() { rt_free(p); }
+    // made once, at the size its first use asks for
+    bool ensure(size_t n) { return p || grow(n); }
+    // replaced by a larger one when a call needs more (the old contents are not kept)
+    bool grow(size_t n) {
+        if (n <= bytes) return true;
+        rt_free(p);
+        p = nullptr;
+        bytes = rt_malloc(&p, n) == 0 ? n : 0;
+        if (!bytes) p = nullptr;                  // (whatever a failed allocation left there is not ours to free)
+        return bytes != 0;
+    }
+};
+
 }  // namespace
 
 struct rtStereoNet {
@@ -61,28 +82,15 @@ struct rtStereoNet {
     IExecutionContext* context = nullptr;
     int layers = 0, width = 0, height = 0, max_batch = 1;
     int model = RT_MODEL_RESNET18_2D;
-    void* frame_in[2] = {nullptr, nullptr};       // rt_net_execute_frames: fp32 inputs and disparity for max_batch, made on first use
-    void* frame_disp = nullptr;
-    void* frame_px = nullptr;                     // rt_net_execute_frames_ex, RT_GEOM_FRAME: network-geometry pixels and mask for max_batch
-    void* frame_mask = nullptr;
-    void* points_ws = nullptr;                    // rt_net_execute_frames_3d: rt_disparity_to_points' workspace, grown on demand
-    size_t points_ws_bytes = 0;
-    void* rect[2] = {nullptr, nullptr};           // rt_net_execute_frames_raw: dense rectified frames for max_batch, grown on demand
-    size_t rect_bytes = 0;
-    void* speckle_ws = nullptr;                   // rt_net_execute_frames_filtered: rt_disparity_speckle's workspace for max_batch, made on first use
-    size_t speckle_ws_bytes = 0;
-    ~rtStereoNet() {
+    // The frame path's buffers (run_frames), all for max_batch, none made before a call needs it.
+    DeviceBuffer frame_in[2], frame_disp;         // the engine's three bindings: fp32 inputs and disparity, the same for every entry
+    DeviceBuffer frame_px, frame_mask;            // RT_GEOM_FRAME: network-geometry pixels and mask
+    DeviceBuffer points_ws;                       // compact clouds: rt_disparity_to_points' workspace, grown on demand
+    DeviceBuffer rect[2];                         // raw frames without caller buffers: dense rectified frames, grown on demand
+    DeviceBuffer speckle_ws;                      // with a filter: rt_disparity_speckle's workspace
+    ~rtStereoNet() {                              // (the buffers go after the engine that may still name them)
         if (context) context->destroy();
         if (engine) engine->destroy();
-        rt_free(frame_in[0]);
-        rt_free(frame_in[1]);
-        rt_free(frame_disp);
-        rt_free(frame_px);
-        rt_free(frame_mask);
-        rt_free(points_ws);
-        rt_free(rect[0]);
-        rt_free(rect[1]);
-        rt_free(speckle_ws);
     }
 };
 
@@ -108,6 +116,11 @@ bool parseWeights(rtStereoNet& n, int dtype) {
         off += (size_t)count * el;
     }
     return !n.weights.empty();
+}
+
+// what every execute entry binds: left, right, disp, in that order
+bool bindings_ok(const ICudaEngine& e) {
+    return e.getNbBindings() == 3 && e.getBindingIndex("left") == 0 && e.getBindingIndex("right") == 1 && e.getBindingIndex("disp") == 2;
 }
 
 int build(rtStereoNet** out, int model, int width, int height, int max_batch, int dtype, int max_disp,
@@ -158,12 +171,34 @@ int build(rtStereoNet** out, int model, int width, int height, int max_batch, in
     net->destroy();
     builder->destroy();
     if (!n->engine) return fail("rt_net_create: engine build failed: " + n->log.last_error);
-    if (n->engine->getNbBindings() != 3 || n->engine->getBindingIndex("left") != 0 || n->engine->getBindingIndex("right") != 1 ||
-        n->engine->getBindingIndex("disp") != 2)
-        return fail("rt_net_create: unexpected bindings");
+    if (!bindings_ok(*n->engine)) return fail("rt_net_create: unexpected bindings");
     n->context = n->engine->createExecutionContext();
     if (!n->context) return fail("rt_net_create: context creation failed");
     *out = n.release();
+    return 0;
+}
+
+// a weight file as it lies on the disk
+int read_image(const std::string& fn, const char* path, std::vector<char>& image) {
+    std::ifstream f(path, std::ios::binary | std::ios::ate);
+    if (!f.is_open()) return fail(fn + "cannot open " + path);
+    image.resize((size_t)f.tellg());
+    f.seekg(0);
+    f.read(image.data(), (std::streamsize)image.size());
+    return 0;
+}
+
+// The weight image travels root -> everyone over RCCL: its size first, then its bytes.  comm == NULL is a world of one.
+int broadcast_image(const std::string& fn, rtComm* comm, int root, std::vector<char>& image) {
+    int world = 1, rank = 0;
+    if (comm && rt_comm_info(comm, &world, &rank) != 0) return fail(fn + rt_last_error_string());
+    if (root < 0 || root >= world) return fail(fn + "root is not a rank of the communicator");
+    if (rank == root && image.empty()) return fail(fn + "the root rank has no weight image");
+    uint64_t n = rank == root ? (uint64_t)image.size() : 0;
+    if (comm && rt_comm_broadcast(comm, &n, sizeof(n), root, nullptr) != 0) return fail(fn + rt_last_error_string());
+    if (n == 0 || n > ((uint64_t)1 << 32)) return fail(fn + "implausible weight image size received");
+    image.resize((size_t)n);
+    if (comm && rt_comm_broadcast(comm, image.data(), (size_t)n, root, nullptr) != 0) return fail(fn + rt_last_error_string());
     return 0;
 }
 
@@ -174,12 +209,9 @@ extern "C" const char* rt_net_last_error(void) { return g_net_err.c_str(); }
 extern "C" int rt_net_create(rtStereoNet** net, int model, int width, int height, int max_batch, int dtype, int max_disp,
                              const char* path) {
     if (!path) return fail("rt_net_create: null weights path");
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f.is_open()) return fail(std::string("rt_net_create: cannot open ") + path);
-    std::vector<char> blob((size_t)f.tellg());
-    f.seekg(0);
-    f.read(blob.data(), (std::streamsize)blob.size());
-    return build(net, model, width, height, max_batch, dtype, max_disp, std::move(blob));
+    std::vector<char> image;
+    if (read_image("rt_net_create: ", path, image) != 0) return RT_E_BADARG;
+    return build(net, model, width, height, max_batch, dtype, max_disp, std::move(image));
 }
 
 extern "C" int rt_net_create_from_memory(rtStereoNet** net, int model, int width, int height, int max_batch, int dtype,
@@ -192,16 +224,9 @@ extern "C" int rt_net_create_from_memory(rtStereoNet** net, int model, int width
 // Multi-GPU start-up (include/rt_stereo_net.h): the weight image travels root -> everyone over RCCL, then every rank builds its engine.
 extern "C" int rt_net_create_broadcast(rtStereoNet** net, int model, int width, int height, int max_batch, int dtype, int max_disp,
                                        const void* blob, size_t bytes, rtComm* comm, int root) {
-    int world = 1, rank = 0;
-    if (comm && rt_comm_info(comm, &world, &rank) != 0) return fail(std::string("rt_net_create_broadcast: ") + rt_last_error_string());
-    if (root < 0 || root >= world) return fail("rt_net_create_broadcast: root is not a rank of the communicator");
-    if (rank == root && (!blob || !bytes)) return fail("rt_net_create_broadcast: the root rank has no weight image");
-    uint64_t n = rank == root ? (uint64_t)bytes : 0;
-    if (comm && rt_comm_broadcast(comm, &n, sizeof(n), root, nullptr) != 0) return fail(std::string("rt_net_create_broadcast: ") + rt_last_error_string());
-    if (n == 0 || n > ((uint64_t)1 << 32)) return fail("rt_net_create_broadcast: implausible weight image size received");
-    std::vector<char> image((size_t)n);
-    if (rank == root) memcpy(image.data(), blob, (size_t)n);
-    if (comm && rt_comm_broadcast(comm, image.data(), (size_t)n, root, nullptr) != 0) return fail(std::string("rt_net_create_broadcast: ") + rt_last_error_string());
+    std::vector<char> image;
+    if (blob && bytes) image.assign(static_cast<const char*>(blob), static_cast<const char*>(blob) + bytes);
+    if (broadcast_image("rt_net_create_broadcast: ", comm, root, image) != 0) return RT_E_BADARG;
     return build(net, model, width, height, max_batch, dtype, max_disp, std::move(image));
 }
 
@@ -209,25 +234,11 @@ extern "C" int rt_net_create_opt(rtStereoNet** net, const rtNetOptions* o) {
     if (!o) return fail("rt_net_create_opt: null options");
     std::vector<char> image;
     if (o->weights_path && !o->blob) {
-        std::ifstream f(o->weights_path, std::ios::binary | std::ios::ate);
-        if (!f.is_open()) return fail(std::string("rt_net_create_opt: cannot open ") + o->weights_path);
-        image.resize((size_t)f.tellg());
-        f.seekg(0);
-        f.read(image.data(), (std::streamsize)image.size());
+        if (read_image("rt_net_create_opt: ", o->weights_path, image) != 0) return RT_E_BADARG;
     } else if (o->blob && o->bytes) {
         image.assign(static_cast<const char*>(o->blob), static_cast<const char*>(o->blob) + o->bytes);
     }
-    if (o->comm) {
-        int world = 1, rank = 0;
-        if (rt_comm_info(o->comm, &world, &rank) != 0) return fail(std::string("rt_net_create_opt: ") + rt_last_error_string());
-        if (o->root < 0 || o->root >= world) return fail("rt_net_create_opt: root is not a rank of the communicator");
-        if (rank == o->root && image.empty()) return fail("rt_net_create_opt: the root rank has no weight image");
-        uint64_t n = rank == o->root ? (uint64_t)image.size() : 0;
-        if (rt_comm_broadcast(o->comm, &n, sizeof(n), o->root, nullptr) != 0) return fail(std::string("rt_net_create_opt: ") + rt_last_error_string());
-        if (n == 0 || n > ((uint64_t)1 << 32)) return fail("rt_net_create_opt: implausible weight image size received");
-        image.resize((size_t)n);
-        if (rt_comm_broadcast(o->comm, image.data(), (size_t)n, o->root, nullptr) != 0) return fail(std::string("rt_net_create_opt: ") + rt_last_error_string());
-    }
+    if (o->comm && broadcast_image("rt_net_create_opt: ", o->comm, o->root, image) != 0) return RT_E_BADARG;
     if (image.empty()) return fail("rt_net_create_opt: no weights (weights_path, blob or a broadcast)");
     return build(net, o->model, o->width, o->height, o->max_batch, o->weights_dtype, o->max_disp, std::move(image), o->flags);
 }
@@ -283,9 +294,7 @@ extern "C" int rt_net_create_from_plan(rtStereoNet** out, const void* plan, size
     n->engine = runtime->deserializeCudaEngine(plan, plan_bytes, &factory);
     runtime->destroy();
     if (!n->engine) return fail("rt_net_create_from_plan: " + n->log.last_error);
-    if (n->engine->getNbBindings() != 3 || n->engine->getBindingIndex("left") != 0 || n->engine->getBindingIndex("right") != 1 ||
-        n->engine->getBindingIndex("disp") != 2)
-        return fail("rt_net_create_from_plan: unexpected bindings");
+    if (!bindings_ok(*n->engine)) return fail("rt_net_create_from_plan: unexpected bindings");
     n->max_batch = n->engine->getMaxBatchSize();
     // a plan knows its input size; only ResNet-18 2D has one (rt_net_serialize fails for the 3-D models' plugins)
     const Dims in = n->engine->getBindingDimensions(0);
@@ -307,123 +316,51 @@ extern "C" int rt_net_execute(rtStereoNet* net, const void* left, const void* ri
     return 0;
 }
 
-// The ROS node's computeOutputs (stereo_dnn_ros_node.cpp:60-103) after the H2D copy of the raw frames, and the sample app's result path
-// (sample_app/main.cpp:321-330), on the device.
-extern "C" int rt_net_execute_frames(rtStereoNet* net, const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step,
-                                     int encoding, void* disp, int disp_kind, int batch, rtStream stream) {
-    if (!net || !net->context || !left_u8 || !right_u8 || !disp) return fail("rt_net_execute_frames: null pointer");
-    if (batch < 1 || batch > net->max_batch)
-        return fail("rt_net_execute_frames: batch " + std::to_string(batch) + " outside 1.." + std::to_string(net->max_batch));
-    if (disp_kind != RT_DISP_NET && disp_kind != RT_DISP_PIXELS_F32 && disp_kind != RT_DISP_KITTI_U16)
-        return fail("rt_net_execute_frames: unknown disp_kind " + std::to_string(disp_kind));
-    if (encoding < RT_ENC_BGR8 || encoding > RT_ENC_RGBA8) return fail("rt_net_execute_frames: unknown encoding " + std::to_string(encoding));
-    const int64_t pixels = (int64_t)net->height * net->width;
-    for (void** p : {&net->frame_in[0], &net->frame_in[1], &net->frame_disp}) {
-        const size_t bytes = (size_t)net->max_batch * pixels * (p == &net->frame_disp ? 1 : 3) * sizeof(float);
-        if (!*p && rt_malloc(p, bytes) != 0) return fail(std::string("rt_net_execute_frames: ") + rt_last_error_string());
-    }
-    // (argument errors of the pre-processing -- short step, up-scaling, factors above 6 -- are found before anything is written)
-    if (rt_preprocess_frames_u8(left_u8, right_u8, src_h, src_w, src_step, encoding, net->frame_in[0], net->frame_in[1], net->height,
-                                net->width, batch, stream) != 0)
-        return fail(std::string("rt_net_execute_frames: ") + rt_last_error_string());
-    void* bindings[3] = {net->frame_in[0], net->frame_in[1], net->frame_disp};
-    const bool ok = stream ? net->context->enqueue(batch, bindings, (cudaStream_t)stream, nullptr) : net->context->execute(batch, bindings);
-    if (!ok) return fail("rt_net_execute_frames: " + net->log.last_error);
-    // ResNet-18 2D's sigmoid output is disparity / width; the 3-D models' soft-argmin is in pixels (sample_app/main.cpp:325-327)
-    const float scale = net->model == RT_MODEL_RESNET18_2D ? (float)net->width : 1.f;
-    const int64_t n = batch * pixels;
-    int rc = 0;
-    if (disp_kind == RT_DISP_NET) rc = rt_memcpy_d2d(disp, net->frame_disp, (size_t)n * sizeof(float), stream);
-    else if (disp_kind == RT_DISP_PIXELS_F32) rc = rt_disparity_scale(net->frame_disp, disp, n, scale, stream);
-    else rc = rt_disparity_to_u16(net->frame_disp, disp, n, 256.f * scale, stream);
-    if (rc == 0 && !stream) rc = rt_stream_sync(nullptr);
-    if (rc != 0) return fail(std::string("rt_net_execute_frames: ") + rt_last_error_string());
-    return 0;
-}
-
-// rt_net_execute_frames with a left-right consistency check: the mirrored, swapped pair rides as the second half of one engine batch.
-// Same three bindings as rt_net_execute_frames (the buffers are sized for max_batch there, and 2 * batch <= max_batch here), so the
-// engine's graph for batch 2b lives beside the one rt_net_execute_frames made for batch b.
-extern "C" int rt_net_execute_frames_lr(rtStereoNet* net, const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step,
-                                        int encoding, void* disp, int disp_kind, void* mask_u8, void* disp_right, void* valid_count,
-                                        float max_diff_px, int batch, rtStream stream) {
-    if (!net || !net->context || !left_u8 || !right_u8 || !disp) return fail("rt_net_execute_frames_lr: null pointer");
-    if (batch < 1 || 2 * (int64_t)batch > net->max_batch)
-        return fail("rt_net_execute_frames_lr: batch " + std::to_string(batch) + " needs an engine batch of " + std::to_string(2 * (int64_t)batch) +
-                    ", max_batch is " + std::to_string(net->max_batch));
-    if (disp_kind != RT_DISP_NET && disp_kind != RT_DISP_PIXELS_F32 && disp_kind != RT_DISP_KITTI_U16)
-        return fail("rt_net_execute_frames_lr: unknown disp_kind " + std::to_string(disp_kind));
-    if (encoding < RT_ENC_BGR8 || encoding > RT_ENC_RGBA8) return fail("rt_net_execute_frames_lr: unknown encoding " + std::to_string(encoding));
-    if (!(max_diff_px >= 0.f)) return fail("rt_net_execute_frames_lr: max_diff_px must be a number >= 0");
-    const int64_t pixels = (int64_t)net->height * net->width;
-    for (void** p : {&net->frame_in[0], &net->frame_in[1], &net->frame_disp}) {
-        const size_t bytes = (size_t)net->max_batch * pixels * (p == &net->frame_disp ? 1 : 3) * sizeof(float);
-        if (!*p && rt_malloc(p, bytes) != 0) return fail(std::string("rt_net_execute_frames_lr: ") + rt_last_error_string());
-    }
-    if (rt_preprocess_frames_u8_lr(left_u8, right_u8, src_h, src_w, src_step, encoding, net->frame_in[0], net->frame_in[1], net->height,
-                                   net->width, batch, stream) != 0)
-        return fail(std::string("rt_net_execute_frames_lr: ") + rt_last_error_string());
-    void* bindings[3] = {net->frame_in[0], net->frame_in[1], net->frame_disp};
-    const bool ok = stream ? net->context->enqueue(2 * batch, bindings, (cudaStream_t)stream, nullptr) : net->context->execute(2 * batch, bindings);
-    if (!ok) return fail("rt_net_execute_frames_lr: " + net->log.last_error);
-    const float scale = net->model == RT_MODEL_RESNET18_2D ? (float)net->width : 1.f;       // as rt_net_execute_frames
-    int rc = rt_lr_consistency(net->frame_disp, batch, net->height, net->width, scale, max_diff_px, disp, disp_kind, mask_u8, disp_right,
-                               valid_count, stream);
-    if (rc == 0 && !stream) rc = rt_stream_sync(nullptr);
-    if (rc != 0) return fail(std::string("rt_net_execute_frames_lr: ") + rt_last_error_string());
-    return 0;
-}
-
-// The DNN node's disparity and the viz node's panel (stereo_dnn_ros_viz_node.cpp:81-130) from one call.  What only the panel can refuse
-// is checked first, so that an error writes nothing; everything else is refused by the wrapped call before it launches anything.
-extern "C" int rt_net_execute_frames_viz(rtStereoNet* net, const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step,
-                                         int encoding, void* disp_px, void* viz_rgb8, int64_t viz_step, float max_disp, float max_diff_px,
-                                         void* mask_u8, void* valid_count, int batch, rtStream stream) {
-    if (!net || !net->context || !left_u8 || !right_u8 || !disp_px || !viz_rgb8) return fail("rt_net_execute_frames_viz: null pointer");
-    if (!(max_disp > 0.f && max_disp <= 3.402823466e38f)) return fail("rt_net_execute_frames_viz: max_disp must be a number > 0");
-    if (viz_step < 6 * (int64_t)net->width)
-        return fail("rt_net_execute_frames_viz: viz_step " + std::to_string(viz_step) + " is shorter than " + std::to_string(2 * net->width) +
-                    " pixels of 3 bytes");
-    if (max_diff_px != max_diff_px) return fail("rt_net_execute_frames_viz: max_diff_px is not a number");
-    const bool check = max_diff_px >= 0.f;
-    if (!check && (mask_u8 || valid_count)) return fail("rt_net_execute_frames_viz: mask_u8 and valid_count need a check (max_diff_px >= 0)");
-    const int rc = check ? rt_net_execute_frames_lr(net, left_u8, right_u8, src_h, src_w, src_step, encoding, disp_px, RT_DISP_PIXELS_F32, mask_u8,
-                                                    nullptr, valid_count, max_diff_px, batch, stream)
-                         : rt_net_execute_frames(net, left_u8, right_u8, src_h, src_w, src_step, encoding, disp_px, RT_DISP_PIXELS_F32, batch, stream);
-    if (rc != 0) return rc;                            // (the wrapped call has set the message)
-    int vrc = rt_viz_mosaic_u8(left_u8, right_u8, src_h, src_w, src_step, encoding, disp_px, net->height, net->width, max_disp, viz_rgb8,
-                               viz_step, batch, stream);
-    if (vrc == 0 && !stream) vrc = rt_stream_sync(nullptr);
-    if (vrc != 0) return fail(std::string("rt_net_execute_frames_viz: ") + rt_last_error_string());
-    return 0;
-}
-
-// Frames of any size in, disparity in the frame's geometry out.  RT_RESIZE_AREA_DOWN with RT_GEOM_NET is the two entries above, called
-// as they are; everything else is the same sequence with rt_preprocess_frames_u8_cv in front and / or rt_disparity_to_frame behind.
-// Whatever an op-level call can refuse is refused by the front end, before anything is written: the back end's limits are the front
-// end's, and its other arguments are checked here.
-// d != NULL: rt_net_execute_frames_3d -- frame geometry only, rt_disparity_to_points behind the network, c->disp optional
-// r != NULL: rt_net_execute_frames_raw -- c's frames are raw; one rt_rectify_frames_u8 launch in front, everything else on its output
-// sp != NULL: rt_net_execute_frames_filtered -- frame geometry only, one rt_disparity_speckle between the step that makes network-geometry
-//            pixels and the back end, which then always gets a mask
+// ---- the camera-frame path ---------------------------------------------------------------------------------------------------------------
+// The seven rt_net_execute_frames* entries fill a FrameJob and make the checks that are theirs alone; run_frames does everything else, once:
+//   validate everything -> make or grow the net's buffers -> [rt_rectify_frames_u8] -> rt_preprocess_frames_u8 / _u8_lr / _u8_cv
+//   -> one engine pass at batch (2 * batch with a check) on the net's three bindings
+//   -> [rt_lr_consistency | rt_disparity_scale] -> [rt_disparity_speckle]
+//   -> one back end: network geometry (copy, scale or 16-bit; with a check rt_lr_consistency is the back end), rt_disparity_to_frame or
+//      rt_disparity_to_points
+//   -> [rt_viz_mosaic_u8] -> one rt_stream_sync when there is no stream.
+// It is the ROS node's computeOutputs (stereo_dnn_ros_node.cpp:60-103) after the H2D copy of the raw frames, the sample app's result path
+// (sample_app/main.cpp:321-330) and the viz node's panel (stereo_dnn_ros_viz_node.cpp:81-130), on the device.  Whatever an op-level call
+// can refuse is refused before anything is written: by the checks here, which precede the rectify launch, or by the front end, whose
+// limits are the back end's.
 namespace {
-int execute_frames_ex(const std::string& fn, rtStereoNet* net, const rtFrameCall* c, const rtDepthCall* d, const rtRectifyCall* r,
-                      const rtSpeckleCall* sp, rtStream stream) {
+
+struct FrameJob {
+    const rtFrameCall* c = nullptr;                // frames and their geometry, resize, output geometry, disparity and its kind, check, batch
+    bool need_check = false;                       // rt_net_execute_frames_lr: a tolerance is not optional
+    void* disp_right = nullptr;                    // ... and the right view's disparity comes out
+    const rtDepthCall* d = nullptr;                // rt_disparity_to_points in the place of rt_disparity_to_frame; c->disp optional
+    const rtRectifyCall* r = nullptr;              // c's frames are raw: everything else runs on their rectified form
+    const rtSpeckleCall* sp = nullptr;             // rt_disparity_speckle in network geometry; the back end then always gets a mask
+    void* viz_rgb8 = nullptr;                      // the viz node's panel of c's frames and c->disp
+    int64_t viz_step = 0;
+    float max_disp = 0.f;
+};
+
+int run_frames(const std::string& fn, rtStereoNet* net, const FrameJob& j, rtStream stream) {
+    const rtFrameCall* c = j.c;
+    const rtDepthCall* d = j.d;
+    const rtRectifyCall* r = j.r;
+    const rtSpeckleCall* sp = j.sp;
     if (!net || !net->context || !c) return fail(fn + "null pointer");
-    if (r && r->struct_bytes != sizeof(rtRectifyCall))
-        return fail(fn + "struct_bytes " + std::to_string(r->struct_bytes) + " is not sizeof(rtRectifyCall) = " + std::to_string(sizeof(rtRectifyCall)));
-    if (c->struct_bytes != sizeof(rtFrameCall))
-        return fail(fn + "struct_bytes " + std::to_string(c->struct_bytes) + " is not sizeof(rtFrameCall) = " + std::to_string(sizeof(rtFrameCall)));
-    if (d && d->struct_bytes != sizeof(rtDepthCall))
-        return fail(fn + "struct_bytes " + std::to_string(d->struct_bytes) + " is not sizeof(rtDepthCall) = " + std::to_string(sizeof(rtDepthCall)));
-    if (sp && sp->struct_bytes != sizeof(rtSpeckleCall))
-        return fail(fn + "struct_bytes " + std::to_string(sp->struct_bytes) + " is not sizeof(rtSpeckleCall) = " + std::to_string(sizeof(rtSpeckleCall)));
+    const auto wrong_size = [&fn](size_t got, size_t want, const char* type) {
+        return fail(fn + "struct_bytes " + std::to_string(got) + " is not sizeof(" + type + ") = " + std::to_string(want));
+    };
+    if (r && r->struct_bytes != sizeof(rtRectifyCall)) return wrong_size(r->struct_bytes, sizeof(rtRectifyCall), "rtRectifyCall");
+    if (c->struct_bytes != sizeof(rtFrameCall)) return wrong_size(c->struct_bytes, sizeof(rtFrameCall), "rtFrameCall");
+    if (d && d->struct_bytes != sizeof(rtDepthCall)) return wrong_size(d->struct_bytes, sizeof(rtDepthCall), "rtDepthCall");
+    if (sp && sp->struct_bytes != sizeof(rtSpeckleCall)) return wrong_size(sp->struct_bytes, sizeof(rtSpeckleCall), "rtSpeckleCall");
     if (!c->left_u8 || !c->right_u8 || (!d && !c->disp)) return fail(fn + "null pointer");
     if (c->resize != RT_RESIZE_AREA_DOWN && c->resize != RT_RESIZE_CV_AREA) return fail(fn + "unknown resize " + std::to_string(c->resize));
     if (c->geometry != RT_GEOM_NET && c->geometry != RT_GEOM_FRAME) return fail(fn + "unknown geometry " + std::to_string(c->geometry));
     if ((!d || c->disp) && c->disp_kind != RT_DISP_NET && c->disp_kind != RT_DISP_PIXELS_F32 && c->disp_kind != RT_DISP_KITTI_U16)
         return fail(fn + "unknown disp_kind " + std::to_string(c->disp_kind));
-    if (d) {                                           // what only rt_disparity_to_points can refuse, so that an error writes nothing
+    if (d) {                                           // what only rt_disparity_to_points can refuse
         constexpr float kMax = 3.402823466e38f;
         const rtStereoCamera& k = d->camera;
         if (c->geometry != RT_GEOM_FRAME) {
@@ -451,6 +388,7 @@ int execute_frames_ex(const std::string& fn, rtStereoNet* net, const rtFrameCall
         if (!(sp->max_diff_px >= 0.f && sp->max_diff_px <= 3.402823466e38f)) return fail(fn + "speckle max_diff_px must be a finite number >= 0");
     }
     if (c->encoding < RT_ENC_BGR8 || c->encoding > RT_ENC_RGBA8) return fail(fn + "unknown encoding " + std::to_string(c->encoding));
+    if (j.need_check && !(c->max_diff_px >= 0.f)) return fail(fn + "max_diff_px must be a number >= 0");
     if (c->max_diff_px != c->max_diff_px) return fail(fn + "max_diff_px is not a number");
     const bool check = c->max_diff_px >= 0.f;
     if (!check && !sp && (c->mask_u8 || c->valid_count)) return fail(fn + "mask_u8 and valid_count need a check (max_diff_px >= 0)");
@@ -458,15 +396,16 @@ int execute_frames_ex(const std::string& fn, rtStereoNet* net, const rtFrameCall
     if (batch < 1 || (int64_t)(check ? 2 : 1) * batch > net->max_batch)
         return fail(fn + "batch " + std::to_string(batch) + (check ? " with a check" : "") + " needs an engine batch of " +
                     std::to_string((int64_t)(check ? 2 : 1) * batch) + ", max_batch is " + std::to_string(net->max_batch));
-    if (c->geometry == RT_GEOM_FRAME && (!d || c->disp) && c->disp_kind == RT_DISP_NET) {
+    const bool frame = c->geometry == RT_GEOM_FRAME;   // (with d or sp: always)
+    if (frame && (!d || c->disp) && c->disp_kind == RT_DISP_NET) {
         fail(fn + "RT_GEOM_FRAME needs a disparity in pixels (RT_DISP_PIXELS_F32 / RT_DISP_KITTI_U16), not RT_DISP_NET");
         return RT_E_UNSUPPORTED;
     }
+    const int H = net->height, W = net->width;
     rtFrameCall rectified;
     if (r) {
         // What the front end and rt_rectify_frames_u8 would refuse, found here: behind the rectify launch an error could no longer
-        // write nothing.  (The back end's limits are the front end's.)
-        const int H = net->height, W = net->width;
+        // write nothing.
         const int bpp = c->encoding == RT_ENC_BGRA8 || c->encoding == RT_ENC_RGBA8 ? 4 : 3;
         if (c->src_h < 1 || c->src_w < 1 || c->src_h > (1 << 24) || c->src_w > (1 << 24) || (int64_t)c->src_h * c->src_w >= ((int64_t)1 << 31) ||
             batch > 32767)
@@ -496,17 +435,9 @@ int execute_frames_ex(const std::string& fn, rtStereoNet* net, const rtFrameCall
             rectified.src_step = r->rect_step;
         } else {
             const size_t need = (size_t)net->max_batch * c->src_h * c->src_w * bpp;
-            if (need > net->rect_bytes) {
-                for (void*& p : net->rect) {
-                    rt_free(p);
-                    p = nullptr;
-                }
-                net->rect_bytes = 0;
-                if (rt_malloc(&net->rect[0], need) != 0 || rt_malloc(&net->rect[1], need) != 0) return fail(fn + rt_last_error_string());
-                net->rect_bytes = need;
-            }
-            rectified.left_u8 = net->rect[0];
-            rectified.right_u8 = net->rect[1];
+            if (!net->rect[0].grow(need) || !net->rect[1].grow(need)) return fail(fn + rt_last_error_string());
+            rectified.left_u8 = net->rect[0].p;
+            rectified.right_u8 = net->rect[1].p;
             rectified.src_step = (int64_t)c->src_w * bpp;
         }
         if (rt_rectify_frames_u8(c->left_u8, c->right_u8, c->src_h, c->src_w, c->src_step, c->encoding, &r->left, &r->right,
@@ -515,111 +446,168 @@ int execute_frames_ex(const std::string& fn, rtStereoNet* net, const rtFrameCall
             return fail(fn + rt_last_error_string());
         c = &rectified;
     }
-    if (!d && c->resize == RT_RESIZE_AREA_DOWN && c->geometry == RT_GEOM_NET)
-        return check ? rt_net_execute_frames_lr(net, c->left_u8, c->right_u8, c->src_h, c->src_w, c->src_step, c->encoding, c->disp, c->disp_kind,
-                                                c->mask_u8, nullptr, c->valid_count, c->max_diff_px, batch, stream)
-                     : rt_net_execute_frames(net, c->left_u8, c->right_u8, c->src_h, c->src_w, c->src_step, c->encoding, c->disp, c->disp_kind, batch,
-                                             stream);
-    const bool frame = c->geometry == RT_GEOM_FRAME;
-    const int H = net->height, W = net->width;
+    // RT_RESIZE_AREA_DOWN into RT_GEOM_NET is what rt_net_execute_frames / _lr do, whichever entry asks: from here on an error reports
+    // under their names (a front end's refusal reads the same through every entry)
+    const std::string as = d || c->resize != RT_RESIZE_AREA_DOWN || frame ? fn : check ? "rt_net_execute_frames_lr: " : "rt_net_execute_frames: ";
     const int64_t pixels = (int64_t)H * W;
-    for (void** p : {&net->frame_in[0], &net->frame_in[1], &net->frame_disp}) {
-        const size_t bytes = (size_t)net->max_batch * pixels * (p == &net->frame_disp ? 1 : 3) * sizeof(float);
-        if (!*p && rt_malloc(p, bytes) != 0) return fail(fn + rt_last_error_string());
-    }
-    if (frame) {
-        if (!net->frame_px && rt_malloc(&net->frame_px, (size_t)net->max_batch * pixels * sizeof(float)) != 0) return fail(fn + rt_last_error_string());
-        if (!net->frame_mask && rt_malloc(&net->frame_mask, (size_t)net->max_batch * pixels) != 0) return fail(fn + rt_last_error_string());
-    }
-    const bool compact = d && (d->points_compact || d->count);
-    if (compact) {
-        const size_t need = rt_points_workspace_bytes(net->max_batch, c->src_h, c->src_w);      // (0 for sizes the front end refuses below)
-        if (need > net->points_ws_bytes) {
-            rt_free(net->points_ws);
-            net->points_ws = nullptr;
-            net->points_ws_bytes = 0;
-            if (rt_malloc(&net->points_ws, need) != 0) return fail(fn + rt_last_error_string());
-            net->points_ws_bytes = need;
-        }
-    }
-    if (sp && !net->speckle_ws) {
+    const size_t plane = (size_t)net->max_batch * pixels;
+    if (!net->frame_in[0].ensure(3 * plane * sizeof(float)) || !net->frame_in[1].ensure(3 * plane * sizeof(float)) ||
+        !net->frame_disp.ensure(plane * sizeof(float)))
+        return fail(as + rt_last_error_string());
+    if (frame && (!net->frame_px.ensure(plane * sizeof(float)) || !net->frame_mask.ensure(plane))) return fail(as + rt_last_error_string());
+    // (rt_points_workspace_bytes is 0 for sizes the front end refuses below)
+    if (d && (d->points_compact || d->count) && !net->points_ws.grow(rt_points_workspace_bytes(net->max_batch, c->src_h, c->src_w)))
+        return fail(as + rt_last_error_string());
+    if (sp && !net->speckle_ws.p) {
         const size_t need = rt_speckle_workspace_bytes(net->max_batch, H, W);
-        if (need == 0) return fail(fn + "the network's size is beyond the speckle filter's limits");
-        if (rt_malloc(&net->speckle_ws, need) != 0) return fail(fn + rt_last_error_string());
-        net->speckle_ws_bytes = need;
+        if (need == 0) return fail(as + "the network's size is beyond the speckle filter's limits");
+        if (!net->speckle_ws.ensure(need)) return fail(as + rt_last_error_string());
     }
+    // (argument errors of the pre-processing -- short step, up-scaling, factors above 6 -- are found before anything is written)
     int rc;
     if (c->resize == RT_RESIZE_CV_AREA)
-        rc = rt_preprocess_frames_u8_cv(c->left_u8, c->right_u8, c->src_h, c->src_w, c->src_step, c->encoding, net->frame_in[0], net->frame_in[1], H,
+        rc = rt_preprocess_frames_u8_cv(c->left_u8, c->right_u8, c->src_h, c->src_w, c->src_step, c->encoding, net->frame_in[0].p, net->frame_in[1].p, H,
                                         W, batch, check ? 1 : 0, stream);
     else
         rc = (check ? rt_preprocess_frames_u8_lr : rt_preprocess_frames_u8)(c->left_u8, c->right_u8, c->src_h, c->src_w, c->src_step, c->encoding,
-                                                                            net->frame_in[0], net->frame_in[1], H, W, batch, stream);
-    if (rc != 0) return fail(fn + rt_last_error_string());
-    void* bindings[3] = {net->frame_in[0], net->frame_in[1], net->frame_disp};
+                                                                            net->frame_in[0].p, net->frame_in[1].p, H, W, batch, stream);
+    if (rc != 0) return fail(as + rt_last_error_string());
+    // The same three bindings for every entry (sized for max_batch, and 2 * batch <= max_batch with a check), so the engine's graph for
+    // batch 2b lives beside the one for batch b.
+    void* bindings[3] = {net->frame_in[0].p, net->frame_in[1].p, net->frame_disp.p};
     const bool ok = stream ? net->context->enqueue(engine_batch, bindings, (cudaStream_t)stream, nullptr) : net->context->execute(engine_batch, bindings);
-    if (!ok) return fail(fn + net->log.last_error);
-    const float scale = net->model == RT_MODEL_RESNET18_2D ? (float)W : 1.f;            // as rt_net_execute_frames
+    if (!ok) return fail(as + net->log.last_error);
+    // ResNet-18 2D's sigmoid output is disparity / width; the 3-D models' soft-argmin is in pixels (sample_app/main.cpp:325-327)
+    const float scale = net->model == RT_MODEL_RESNET18_2D ? (float)W : 1.f;
     const int64_t n = batch * pixels;
-    if (!frame) {                                      // (never with d or sp: both are frame geometry only)
-        if (check) rc = rt_lr_consistency(net->frame_disp, batch, H, W, scale, c->max_diff_px, c->disp, c->disp_kind, c->mask_u8, nullptr, c->valid_count, stream);
-        else if (c->disp_kind == RT_DISP_NET) rc = rt_memcpy_d2d(c->disp, net->frame_disp, (size_t)n * sizeof(float), stream);
-        else if (c->disp_kind == RT_DISP_PIXELS_F32) rc = rt_disparity_scale(net->frame_disp, c->disp, n, scale, stream);
-        else rc = rt_disparity_to_u16(net->frame_disp, c->disp, n, 256.f * scale, stream);
+    if (!frame) {
+        if (check) rc = rt_lr_consistency(net->frame_disp.p, batch, H, W, scale, c->max_diff_px, c->disp, c->disp_kind, c->mask_u8, j.disp_right, c->valid_count, stream);
+        else if (c->disp_kind == RT_DISP_NET) rc = rt_memcpy_d2d(c->disp, net->frame_disp.p, (size_t)n * sizeof(float), stream);
+        else if (c->disp_kind == RT_DISP_PIXELS_F32) rc = rt_disparity_scale(net->frame_disp.p, c->disp, n, scale, stream);
+        else rc = rt_disparity_to_u16(net->frame_disp.p, c->disp, n, 256.f * scale, stream);
     } else {
-        const void* px = net->frame_disp;              // the 3-D models' output is in pixels already
+        const void* px = net->frame_disp.p;            // the 3-D models' output is in pixels already
         const void* mask = nullptr;
         if (check) {
-            rc = rt_lr_consistency(net->frame_disp, batch, H, W, scale, c->max_diff_px, net->frame_px, RT_DISP_PIXELS_F32, net->frame_mask, nullptr, nullptr, stream);
-            px = net->frame_px;
-            mask = net->frame_mask;
+            rc = rt_lr_consistency(net->frame_disp.p, batch, H, W, scale, c->max_diff_px, net->frame_px.p, RT_DISP_PIXELS_F32, net->frame_mask.p, nullptr, nullptr, stream);
+            px = net->frame_px.p;
+            mask = net->frame_mask.p;
         } else if (net->model == RT_MODEL_RESNET18_2D) {
-            rc = rt_disparity_scale(net->frame_disp, net->frame_px, n, scale, stream);
-            px = net->frame_px;
+            rc = rt_disparity_scale(net->frame_disp.p, net->frame_px.p, n, scale, stream);
+            px = net->frame_px.p;
         }
         if (rc == 0 && sp) {                           // in place on frame_px / frame_mask, or out of place from frame_disp where no step ran
-            rc = rt_disparity_speckle(px, mask, batch, H, W, sp->max_size, sp->max_diff_px, net->frame_px, net->frame_mask, nullptr, net->speckle_ws,
-                                      net->speckle_ws_bytes, stream);
-            px = net->frame_px;
-            mask = net->frame_mask;
+            rc = rt_disparity_speckle(px, mask, batch, H, W, sp->max_size, sp->max_diff_px, net->frame_px.p, net->frame_mask.p, nullptr, net->speckle_ws.p,
+                                      net->speckle_ws.bytes, stream);
+            px = net->frame_px.p;
+            mask = net->frame_mask.p;
         }
         // (without a mask c->mask_u8 and c->valid_count are NULL: checked above)
-        if (rc == 0 && d)                              // rt_disparity_to_points in the place of rt_disparity_to_frame
+        if (rc == 0 && d)
             rc = rt_disparity_to_points(px, mask, batch, H, W, c->src_h, c->src_w, &d->camera, d->min_depth, d->max_depth, c->left_u8, c->src_step,
                                         c->encoding, c->disp, c->disp_kind, c->mask_u8, c->valid_count, d->depth, d->depth_kind, d->points,
-                                        d->points_compact, d->count, net->points_ws, net->points_ws_bytes, stream);
+                                        d->points_compact, d->count, net->points_ws.p, net->points_ws.bytes, stream);
         else if (rc == 0)
             rc = rt_disparity_to_frame(px, mask, batch, H, W, c->disp, c->disp_kind, c->src_h, c->src_w, c->mask_u8, c->valid_count, stream);
     }
+    if (rc != 0) return fail(as + rt_last_error_string());
+    if (j.viz_rgb8)
+        rc = rt_viz_mosaic_u8(c->left_u8, c->right_u8, c->src_h, c->src_w, c->src_step, c->encoding, c->disp, H, W, j.max_disp, j.viz_rgb8, j.viz_step,
+                              batch, stream);
     if (rc == 0 && !stream) rc = rt_stream_sync(nullptr);
-    if (rc != 0) return fail(fn + rt_last_error_string());
+    if (rc != 0) return fail((j.viz_rgb8 ? "rt_net_execute_frames_viz: " : as) + rt_last_error_string());
     return 0;
 }
+
+// rt_net_execute_frames (need_check off) and rt_net_execute_frames_lr (on), and rt_net_execute_frames_viz behind its own checks: flat
+// arguments, RT_RESIZE_AREA_DOWN into RT_GEOM_NET, and their own words for a batch that does not fit.
+int run_flat(rtStereoNet* net, const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step, int encoding, void* disp,
+             int disp_kind, float max_diff_px, void* mask_u8, void* valid_count, int batch, FrameJob j, rtStream stream) {
+    const std::string fn = j.need_check ? "rt_net_execute_frames_lr: " : "rt_net_execute_frames: ";
+    if (!net || !net->context || !left_u8 || !right_u8 || !disp) return fail(fn + "null pointer");
+    if (batch < 1 || (int64_t)(j.need_check ? 2 : 1) * batch > net->max_batch)
+        return fail(fn + "batch " + std::to_string(batch) +
+                    (j.need_check ? " needs an engine batch of " + std::to_string(2 * (int64_t)batch) + ", max_batch is " : " outside 1..") +
+                    std::to_string(net->max_batch));
+    const rtFrameCall c = {sizeof(rtFrameCall), left_u8, right_u8, src_h, src_w, src_step, encoding, RT_RESIZE_AREA_DOWN, disp, disp_kind, RT_GEOM_NET,
+                           max_diff_px, mask_u8, valid_count, batch};
+    j.c = &c;
+    return run_frames(fn, net, j, stream);
+}
+
+// the four entries that take an rtFrameCall: each optional part that is absent leaves the entry below it, which also gives the call its name
+int run_call(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out, const rtRectifyCall* rect, const rtSpeckleCall* speckle,
+             rtStream stream) {
+    FrameJob j;
+    j.c = call;
+    j.d = out;
+    j.r = rect;
+    j.sp = speckle;
+    return run_frames(speckle ? "rt_net_execute_frames_filtered: " : rect ? "rt_net_execute_frames_raw: " : out ? "rt_net_execute_frames_3d: "
+                                                                                                                : "rt_net_execute_frames_ex: ",
+                      net, j, stream);
+}
+
 }  // namespace
 
+extern "C" int rt_net_execute_frames(rtStereoNet* net, const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step,
+                                     int encoding, void* disp, int disp_kind, int batch, rtStream stream) {
+    return run_flat(net, left_u8, right_u8, src_h, src_w, src_step, encoding, disp, disp_kind, -1.f, nullptr, nullptr, batch, FrameJob(), stream);
+}
+
+// rt_net_execute_frames with a left-right consistency check: the mirrored, swapped pair rides as the second half of one engine batch.
+extern "C" int rt_net_execute_frames_lr(rtStereoNet* net, const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step,
+                                        int encoding, void* disp, int disp_kind, void* mask_u8, void* disp_right, void* valid_count,
+                                        float max_diff_px, int batch, rtStream stream) {
+    FrameJob j;
+    j.need_check = true;
+    j.disp_right = disp_right;
+    return run_flat(net, left_u8, right_u8, src_h, src_w, src_step, encoding, disp, disp_kind, max_diff_px, mask_u8, valid_count, batch, j, stream);
+}
+
+// The DNN node's disparity and the viz node's panel from one call.  What only the panel can refuse is checked first, so that an error
+// writes nothing; everything else is refused as rt_net_execute_frames / _lr refuse it.
+extern "C" int rt_net_execute_frames_viz(rtStereoNet* net, const void* left_u8, const void* right_u8, int src_h, int src_w, int64_t src_step,
+                                         int encoding, void* disp_px, void* viz_rgb8, int64_t viz_step, float max_disp, float max_diff_px,
+                                         void* mask_u8, void* valid_count, int batch, rtStream stream) {
+    if (!net || !net->context || !left_u8 || !right_u8 || !disp_px || !viz_rgb8) return fail("rt_net_execute_frames_viz: null pointer");
+    if (!(max_disp > 0.f && max_disp <= 3.402823466e38f)) return fail("rt_net_execute_frames_viz: max_disp must be a number > 0");
+    if (viz_step < 6 * (int64_t)net->width)
+        return fail("rt_net_execute_frames_viz: viz_step " + std::to_string(viz_step) + " is shorter than " + std::to_string(2 * net->width) +
+                    " pixels of 3 bytes");
+    if (max_diff_px != max_diff_px) return fail("rt_net_execute_frames_viz: max_diff_px is not a number");
+    const bool check = max_diff_px >= 0.f;
+    if (!check && (mask_u8 || valid_count)) return fail("rt_net_execute_frames_viz: mask_u8 and valid_count need a check (max_diff_px >= 0)");
+    FrameJob j;
+    j.need_check = check;
+    j.viz_rgb8 = viz_rgb8;
+    j.viz_step = viz_step;
+    j.max_disp = max_disp;
+    return run_flat(net, left_u8, right_u8, src_h, src_w, src_step, encoding, disp_px, RT_DISP_PIXELS_F32, check ? max_diff_px : -1.f, mask_u8,
+                    valid_count, batch, j, stream);
+}
+
+// Frames of any size in, disparity in the network's or in the frame's geometry out.
 extern "C" int rt_net_execute_frames_ex(rtStereoNet* net, const rtFrameCall* call, rtStream stream) {
-    return execute_frames_ex("rt_net_execute_frames_ex: ", net, call, nullptr, nullptr, nullptr, stream);
+    return run_call(net, call, nullptr, nullptr, nullptr, stream);
 }
 
-// rt_net_execute_frames_ex in frame geometry with depth and / or a point cloud beside (or instead of) the disparity: the same launches,
-// rt_disparity_to_points in the place of rt_disparity_to_frame
+// ... in frame geometry with depth and / or a point cloud beside (or instead of) the disparity
 extern "C" int rt_net_execute_frames_3d(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out, rtStream stream) {
-    if (!out) return execute_frames_ex("rt_net_execute_frames_ex: ", net, call, nullptr, nullptr, nullptr, stream);
-    return execute_frames_ex("rt_net_execute_frames_3d: ", net, call, out, nullptr, nullptr, stream);
+    return run_call(net, call, out, nullptr, nullptr, stream);
 }
 
-// raw frames in: one rt_rectify_frames_u8 launch, then the call above on its output
+// ... from raw frames: one rt_rectify_frames_u8 launch in front, everything else on its output
 extern "C" int rt_net_execute_frames_raw(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out, const rtRectifyCall* rect,
                                          rtStream stream) {
     if (!rect) return fail("rt_net_execute_frames_raw: null pointer");
-    return execute_frames_ex("rt_net_execute_frames_raw: ", net, call, out, rect, nullptr, stream);
+    return run_call(net, call, out, rect, nullptr, stream);
 }
 
-// the same with a speckle filter in network geometry, in front of the resampling; without one, the call above (rect), or the ones above it
+// ... with a speckle filter in network geometry, in front of the resampling
 extern "C" int rt_net_execute_frames_filtered(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out, const rtRectifyCall* rect,
                                               const rtSpeckleCall* speckle, rtStream stream) {
-    if (!speckle) return rect ? rt_net_execute_frames_raw(net, call, out, rect, stream) : rt_net_execute_frames_3d(net, call, out, stream);
-    return execute_frames_ex("rt_net_execute_frames_filtered: ", net, call, out, rect, speckle, stream);
+    return run_call(net, call, out, rect, speckle, stream);
 }
 
 extern "C" int rt_net_profile(rtStereoNet* net, const void* left, const void* right, void* disp, int batch, char* buf,
