@@ -371,6 +371,46 @@ int rt_remap_frames_u8(const void* left_u8, const void* right_u8, int src_h, int
                        const void* map_x_left, const void* map_y_left, const void* map_x_right, const void* map_y_right,
                        void* left_dst, void* right_dst, int dst_h, int dst_w, int64_t dst_step, int batch, rtStream stream);
 
+/* ---- what the camera really sends: mono, Bayer and YUV 4:2:2 (image_proc's debayer and cv_bridge's colour conversion, on the device) ---- */
+/* Wire encodings of sensor_msgs/Image, a set of their own beside RT_ENC_*: only rt_decode_frames_u8 (and rtDecodeCall, rt_stereo_net.h) takes
+ * them, every other call goes on refusing them.  Bytes per pixel: 1, 2, 1, 1, 1, 1, 2, 2.  The Bayer names are those of
+ * sensor_msgs/image_encodings.h: the four letters are the top-left 2 x 2 of the mosaic, row-major -- rggb: row 0 is R G, row 1 is G B;
+ * bggr: B G / G R;  gbrg: G B / R G;  grbg: G R / B G.  (OpenCV's COLOR_Bayer* constants are named after another corner: go by the
+ * pattern, not by those names.) */
+enum { RT_WIRE_MONO8 = 16, RT_WIRE_MONO16 = 17,
+       RT_WIRE_BAYER_RGGB8 = 18, RT_WIRE_BAYER_BGGR8 = 19, RT_WIRE_BAYER_GBRG8 = 20, RT_WIRE_BAYER_GRBG8 = 21,
+       RT_WIRE_YUV422 = 22 /* UYVY */, RT_WIRE_YUV422_YUY2 = 23 /* YUYV */ };
+/* Wire frames -> colour frames, both frames of a pair batch in one launch.  Frames are addressed exactly as rt_preprocess_frames_u8
+ * addresses them (rows `step` bytes apart, frame n at n * h * step; any step, any base alignment); the output is h x w pixels in
+ * dst_encoding (RT_ENC_*), alpha = 255 for the 4-byte encodings; bytes between a row's last pixel and dst_step are not touched.
+ * Integer arithmetic throughout, >> on a negative value is an arithmetic shift (floor).
+ *   MONO8    R = G = B = v.
+ *   MONO16   little-endian, v16 = b[2x] | b[2x+1] << 8;  R = G = B = min(255, (v16 + 127 + ((v16 >> 8) & 1)) >> 8): rint(v16 / 256) with ties
+ *            to even, saturated -- cv_bridge's 16 -> 8 bit conversion, convertTo(CV_8U, 1 / 256.).  is_bigendian images are not supported:
+ *            swap the bytes first.
+ *   BAYER_*8 bilinear demosaicing.  m(y, x) is the mosaic, extended by reflection about the edge sample (BORDER_REFLECT_101): index
+ *            i < 0 is -i, i > n - 1 is 2 (n - 1) - i.  Reflection keeps the colour phase, so one formula serves every pixel.  The site's
+ *            colour is pattern[y & 1][x & 1].  At an R or B site of colour C, with C' the other one of R and B:
+ *              C = m(y,x);   G  = (m(y,x-1) + m(y,x+1) + m(y-1,x) + m(y+1,x) + 2) >> 2;
+ *              C' = (m(y-1,x-1) + m(y-1,x+1) + m(y+1,x-1) + m(y+1,x+1) + 2) >> 2
+ *            At a G site: G = m(y,x); the colour of the horizontal neighbours, pattern[y & 1][(x & 1) ^ 1], is (m(y,x-1) + m(y,x+1) + 1) >> 1
+ *            and the colour of the vertical neighbours is (m(y-1,x) + m(y+1,x) + 1) >> 1.  Needs h >= 2 and w >= 2; odd sizes are legal.
+ *            In the interior this is the arithmetic of OpenCV's bilinear demosaicing (image_proc's default for 8 bit).  At the one-pixel
+ *            frame OpenCV replicates the neighbouring OUTPUT pixel; the reflection here is a deliberate difference.
+ *   YUV422 / YUV422_YUY2   the 4 bytes of a pixel pair are U Y0 V Y1 (YUV422) or Y0 U Y1 V (YUV422_YUY2); w must be even; both pixels of a
+ *            pair share U and V.  OpenCV's integer BT.601 limited-range conversion (cvtColor(COLOR_YUV2BGR_UYVY / _YUY2)), which fits 32-bit
+ *            signed integers:  CY = 1220542, CUB = 2116026, CUG = -409993, CVG = -852492, CVR = 1673527,  y = max(0, Y - 16) * CY,
+ *              R = clamp((y + (1 << 19) + CVR * (V - 128)) >> 20, 0, 255)
+ *              G = clamp((y + (1 << 19) + CVG * (V - 128) + CUG * (U - 128)) >> 20, 0, 255)
+ *              B = clamp((y + (1 << 19) + CUB * (U - 128)) >> 20, 0, 255)
+ * This statement is the target, held by the properties tests/test_decode.py lists; it was not compared with OpenCV's output.
+ * Errors, found before anything is written: a null pointer; a wire_encoding outside RT_WIRE_* (RT_ENC_* values included); a dst_encoding
+ * outside RT_ENC_*; h, w or batch < 1, h > 4 * 65535, w > 2^24, batch > 32767; a Bayer frame with h < 2 or w < 2; an odd w for the two YUV
+ * encodings; a wire_step shorter than w wire pixels; a dst_step shorter than w output pixels; a destination that is a source (or the other
+ * destination). */
+int rt_decode_frames_u8(const void* left_wire, const void* right_wire, int h, int w, int64_t wire_step, int wire_encoding,
+                        void* left_u8, void* right_u8, int64_t dst_step, int dst_encoding /* RT_ENC_* */, int batch, rtStream stream);
+
 /* ---- the viz node's debug panel (ros/packages/stereo_dnn_ros_viz/src/stereo_dnn_ros_viz_node.cpp) ---------------------------- */
 /* KITTI colour scheme of the viz node's dispToColor (:49-79): disp_px (n,1,H,W) fp32 pixels -> rgb8, rows dst_step >= 3W bytes apart,
  * images H * dst_step bytes apart; bytes between 3W and dst_step are not touched.  With the reference's fp32 tables

@@ -209,6 +209,34 @@ typedef struct rtSpeckleCall {
 int rt_net_execute_frames_filtered(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out /* or NULL */,
                                    const rtRectifyCall* rect /* or NULL */, const rtSpeckleCall* speckle /* or NULL */, rtStream stream);
 
+/* What the camera really sends in: mono, Bayer or YUV 4:2:2 frames (rt_stereo.h: RT_WIRE_*, rt_decode_frames_u8, where every conversion is
+ * defined) in front of rt_net_execute_frames_filtered.
+ *   decode == NULL: rt_net_execute_frames_filtered on the same arguments, refusals and error texts included.
+ *   decode != NULL: call->left_u8 / right_u8 are WIRE frames of decode->wire_encoding, rows call->src_step bytes apart, and call->encoding is
+ *                   the RT_ENC_* encoding to decode into.  One rt_decode_frames_u8 launch makes colour frames of the same size -- dense
+ *                   buffers the net owns, made on first use for max_batch and regrown when a larger frame arrives, or the caller's
+ *                   left_color_u8 / right_color_u8 (image_color), rows color_step bytes apart -- and the call then is
+ *                   rt_net_execute_frames_filtered(net, &call2, out, rect, speckle, stream) with call2 = *call, its frame pointers and step
+ *                   replaced by the decoded ones.  Debayering comes before rectification, as in image_proc; rectified frames, the cloud's
+ *                   colour and everything else downstream see call->encoding.
+ * Composition is the definition: every output is bit-identical to those two calls made by hand.  All checks of all five structs are made
+ * before the first launch -- the decode launch -- so an error writes nothing: whatever the wrapped call and its front end refuse (with
+ * call->src_step held against the WIRE pixel size: bad dimensions, a short step, up-scaling under RT_RESIZE_AREA_DOWN, factors outside
+ * [1/6, 6]), whatever rt_decode_frames_u8 refuses, a wrong struct_bytes, one of left_color_u8 / right_color_u8 without the other, a
+ * color_step shorter than a row (or not 0 with NULL), a colour buffer that is a wire buffer or a rectified buffer.  The decode launch runs
+ * outside the engine's graph, so every pointer may rotate in graph mode; stream == NULL: synchronous.  The other rt_net_execute_frames*
+ * entries go on refusing wire encodings: for the viz panel of a Bayer camera, decode with rt_decode_frames_u8 and pass the result on. */
+typedef struct rtDecodeCall {
+    size_t struct_bytes;        /* sizeof(rtDecodeCall) */
+    int wire_encoding;          /* RT_WIRE_*: what call->left_u8 / right_u8 hold, rows call->src_step bytes apart */
+    void* left_color_u8;        /* optional: receive the decoded frames (image_color), src_h x src_w in call->encoding ... */
+    void* right_color_u8;       /* ... both or neither; NULL: dense buffers the net owns */
+    int64_t color_step;         /* row step of those two; 0 with NULL */
+} rtDecodeCall;
+int rt_net_execute_frames_camera(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out /* or NULL */,
+                                 const rtRectifyCall* rect /* or NULL */, const rtSpeckleCall* speckle /* or NULL */,
+                                 const rtDecodeCall* decode /* or NULL */, rtStream stream);
+
 /* Per-launch timing through nvinfer1::IProfiler (single stream, one event pair per launch):
  * writes "name<TAB>milliseconds\n" lines into buf.  Returns 0 or an error. */
 int rt_net_profile(rtStereoNet* net, const void* left, const void* right, void* disp, int batch, char* buf,

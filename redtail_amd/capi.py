@@ -21,6 +21,12 @@ RT_ACT_NONE, RT_ACT_ELU, RT_ACT_SIGMOID = 0, 1, 2
 
 RT_ENC_BGR8, RT_ENC_RGB8, RT_ENC_BGRA8, RT_ENC_RGBA8 = 0, 1, 2, 3     # sensor_msgs/Image encodings (rt_preprocess_frames_u8)
 ENC_BYTES = {RT_ENC_BGR8: 3, RT_ENC_RGB8: 3, RT_ENC_BGRA8: 4, RT_ENC_RGBA8: 4}
+# wire encodings of sensor_msgs/Image that only rt_decode_frames_u8 / rtDecodeCall take: mono, Bayer (the letters are the top-left 2 x 2, row-major), YUV 4:2:2
+RT_WIRE_MONO8, RT_WIRE_MONO16 = 16, 17
+RT_WIRE_BAYER_RGGB8, RT_WIRE_BAYER_BGGR8, RT_WIRE_BAYER_GBRG8, RT_WIRE_BAYER_GRBG8 = 18, 19, 20, 21
+RT_WIRE_YUV422, RT_WIRE_YUV422_YUY2 = 22, 23                          # UYVY, YUYV
+WIRE_BYTES = {RT_WIRE_MONO8: 1, RT_WIRE_MONO16: 2, RT_WIRE_BAYER_RGGB8: 1, RT_WIRE_BAYER_BGGR8: 1, RT_WIRE_BAYER_GBRG8: 1, RT_WIRE_BAYER_GRBG8: 1,
+              RT_WIRE_YUV422: 2, RT_WIRE_YUV422_YUY2: 2}
 RT_DISP_NET, RT_DISP_PIXELS_F32, RT_DISP_KITTI_U16 = 0, 1, 2          # forms of a disparity output (rt_lr_consistency, rt_net_execute_frames)
 RT_DEPTH_M_F32, RT_DEPTH_MM_U16 = 0, 1                                # REP 118 depth images (rt_disparity_to_points)
 RT_HINT_THROUGHPUT = 1     # include/rt_stereo.h
@@ -141,6 +147,7 @@ KERNEL_SYMBOLS = {
     "rt_rectify_maps": (c_int, [POINTER(RectifyCamera), c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "rt_remap_frames_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_int, c_int, c_int64, c_int, c_void_p]),
+    "rt_decode_frames_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "rt_disparity_to_color": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p]),
     "rt_viz_mosaic_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_int64, c_int,
                                  c_void_p]),
@@ -310,6 +317,13 @@ class KernelLib:
         self.check(self.lib.rt_remap_frames_u8(_ptr(left), _ptr(right), src_h, src_w, src_step, encoding, _ptr(map_x_left), _ptr(map_y_left),
                                                _ptr(map_x_right), _ptr(map_y_right), _ptr(left_dst), _ptr(right_dst), dst_h, dst_w, dst_step,
                                                batch, stream), "rt_remap_frames_u8")
+
+    def decode_frames_u8(self, left_wire, right_wire, h, w, wire_step, wire_encoding, left_dst, right_dst, dst_step, dst_encoding=RT_ENC_BGR8,
+                         batch=1, stream=None):
+        """wire frames (RT_WIRE_*: mono8 / mono16, 8-bit Bayer, YUV 4:2:2), rows wire_step bytes apart -> h x w colour frames in dst_encoding
+        (RT_ENC_*), rows dst_step bytes apart, both frames of a pair batch in one launch: grey replication, bilinear demosaicing, BT.601"""
+        self.check(self.lib.rt_decode_frames_u8(_ptr(left_wire), _ptr(right_wire), h, w, wire_step, wire_encoding, _ptr(left_dst), _ptr(right_dst),
+                                                dst_step, dst_encoding, batch, stream), "rt_decode_frames_u8")
 
     def points_workspace_bytes(self, batch, out_h, out_w):
         """bytes of device workspace disparity_to_points needs for a compact cloud or a count"""
@@ -560,6 +574,7 @@ NET_SYMBOLS = {
     "rt_net_execute_frames_3d": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "rt_net_execute_frames_raw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rt_net_execute_frames_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rt_net_execute_frames_camera": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rt_net_profile": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_char_p, c_size_t]),
     "rt_net_num_layers": (c_int, [c_void_p]),
     "rt_net_num_launches": (c_int, [c_void_p]),
@@ -607,6 +622,12 @@ class RectifyCall(ctypes.Structure):
 class SpeckleCall(ctypes.Structure):
     """rtSpeckleCall (include/rt_stereo_net.h)"""
     _fields_ = [("struct_bytes", c_size_t), ("max_size", c_int), ("max_diff_px", c_float)]
+
+
+class DecodeCall(ctypes.Structure):
+    """rtDecodeCall (include/rt_stereo_net.h)"""
+    _fields_ = [("struct_bytes", c_size_t), ("wire_encoding", c_int), ("left_color_u8", c_void_p), ("right_color_u8", c_void_p),
+                ("color_step", c_int64)]
 
 
 def pack_weights(weights, fp16=False):
@@ -874,6 +895,57 @@ class StereoNet:
                                                speckle_range))
         self.netlib.check(self.netlib.lib.rt_net_execute_frames_filtered(self.handle, ctypes.byref(call), out, rect, speckle, stream),
                           "rt_net_execute_frames_filtered")
+
+    def execute_frames_camera(self, left_wire, right_wire, wire_encoding, encoding=RT_ENC_BGR8, speckle_size=None, speckle_range=1.0,
+                              rect_left=None, rect_right=None, camera=None, disp=None, kind=RT_DISP_PIXELS_F32, geometry=RT_GEOM_FRAME,
+                              resize=RT_RESIZE_CV_AREA, max_diff_px=-1.0, mask=None, valid_count=None, min_depth=0.0, max_depth=float("inf"),
+                              depth=None, depth_kind=RT_DEPTH_M_F32, points=None, points_compact=None, count=None, batch=1, stream=None,
+                              src_step=None, src_w=None, struct_bytes=None, depth_struct_bytes=None, no_depth_call=False, left_rect=None,
+                              right_rect=None, rect_step=None, rect_struct_bytes=None, speckle_struct_bytes=None, left_color=None,
+                              right_color=None, color_step=None, decode_struct_bytes=None):
+        """rt_net_execute_frames_camera: what the camera really sends in.  left_wire / right_wire: (N, H, step) uint8 rows of wire_encoding
+        (RT_WIRE_*: mono8 / mono16, 8-bit Bayer, YUV 4:2:2; src_w defaults to step // bytes per wire pixel).  One decode_frames_u8 launch
+        into colour frames of `encoding` (buffers of the net, or left_color / right_color: (N, H, color_step) uint8, color_step defaulting
+        to their row stride), then execute_frames_filtered on them with the same keywords.  wire_encoding=None: no decode, `encoding`
+        frames in, execute_frames_filtered itself."""
+        strides = lambda t: tuple(t.stride()) if hasattr(t, "data_ptr") else tuple(t.strides)
+        if wire_encoding is None:
+            h, w, step = self._frame_geometry("rt_net_execute_frames_camera", left_wire, right_wire, encoding, batch, src_step, src_w)
+        else:
+            shape, st = tuple(left_wire.shape), strides(left_wire)
+            if len(shape) != 3 or tuple(right_wire.shape) != shape or strides(right_wire) != st or st[2] != 1:
+                raise ValueError("wire frames must be two (N,H,step) uint8 batches of the same shape, rows of contiguous bytes")
+            if shape[0] < batch or (batch > 1 and st[0] != shape[1] * st[1]):
+                raise ValueError("frame batch must hold %d frames of %d rows of %d bytes back to back" % (batch, shape[1], st[1]))
+            h, step = shape[1], st[1] if src_step is None else src_step
+            w = src_w if src_w is not None else shape[2] // WIRE_BYTES.get(wire_encoding, 1)
+        call = FrameCall(ctypes.sizeof(FrameCall) if struct_bytes is None else struct_bytes, _ptr(left_wire), _ptr(right_wire), h, w, step, encoding,
+                         resize, _ptr(disp), kind, geometry, max_diff_px, _ptr(mask), _ptr(valid_count), batch)
+        out = None
+        if not no_depth_call:
+            out = ctypes.byref(DepthCall(ctypes.sizeof(DepthCall) if depth_struct_bytes is None else depth_struct_bytes,
+                                         camera if camera is not None else StereoCamera(), min_depth, max_depth, _ptr(depth), depth_kind,
+                                         _ptr(points), _ptr(points_compact), _ptr(count)))
+        rect = None
+        if rect_left is not None or rect_right is not None:
+            if rect_step is None:
+                given = left_rect if left_rect is not None else right_rect
+                rect_step = 0 if given is None else strides(given)[1]
+            rect = ctypes.byref(RectifyCall(ctypes.sizeof(RectifyCall) if rect_struct_bytes is None else rect_struct_bytes, rect_left, rect_right,
+                                            _ptr(left_rect), _ptr(right_rect), rect_step))
+        speckle = None
+        if speckle_size is not None:
+            speckle = ctypes.byref(SpeckleCall(ctypes.sizeof(SpeckleCall) if speckle_struct_bytes is None else speckle_struct_bytes, speckle_size,
+                                               speckle_range))
+        decode = None
+        if wire_encoding is not None:
+            if color_step is None:
+                given = left_color if left_color is not None else right_color
+                color_step = 0 if given is None else strides(given)[1]
+            decode = ctypes.byref(DecodeCall(ctypes.sizeof(DecodeCall) if decode_struct_bytes is None else decode_struct_bytes, wire_encoding,
+                                             _ptr(left_color), _ptr(right_color), color_step))
+        self.netlib.check(self.netlib.lib.rt_net_execute_frames_camera(self.handle, ctypes.byref(call), out, rect, speckle, decode, stream),
+                          "rt_net_execute_frames_camera")
 
     def set_debug(self, on=True):
         """IExecutionContext::setDebugSync: synchronise every launch and range-check the input of every fp16-pipe convolution"""

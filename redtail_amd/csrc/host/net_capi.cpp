@@ -87,6 +87,7 @@ struct rtStereoNet {
     DeviceBuffer frame_px, frame_mask;            // RT_GEOM_FRAME: network-geometry pixels and mask
     DeviceBuffer points_ws;                       // compact clouds: rt_disparity_to_points' workspace, grown on demand
     DeviceBuffer rect[2];                         // raw frames without caller buffers: dense rectified frames, grown on demand
+    DeviceBuffer color[2];                        // wire frames without caller buffers: dense decoded frames, grown on demand
     DeviceBuffer speckle_ws;                      // with a filter: rt_disparity_speckle's workspace
     ~rtStereoNet() {                              // (the buffers go after the engine that may still name them)
         if (context) context->destroy();
@@ -317,7 +318,7 @@ extern "C" int rt_net_execute(rtStereoNet* net, const void* left, const void* ri
 }
 
 // ---- the camera-frame path ---------------------------------------------------------------------------------------------------------------
-// The seven rt_net_execute_frames* entries fill a FrameJob and make the checks that are theirs alone; run_frames does everything else, once:
+// The eight rt_net_execute_frames* entries fill a FrameJob and make the checks that are theirs alone; run_frames does everything else, once:
 //   validate everything -> make or grow the net's buffers -> [rt_rectify_frames_u8] -> rt_preprocess_frames_u8 / _u8_lr / _u8_cv
 //   -> one engine pass at batch (2 * batch with a check) on the net's three bindings
 //   -> [rt_lr_consistency | rt_disparity_scale] -> [rt_disparity_speckle]
@@ -326,8 +327,8 @@ extern "C" int rt_net_execute(rtStereoNet* net, const void* left, const void* ri
 //   -> [rt_viz_mosaic_u8] -> one rt_stream_sync when there is no stream.
 // It is the ROS node's computeOutputs (stereo_dnn_ros_node.cpp:60-103) after the H2D copy of the raw frames, the sample app's result path
 // (sample_app/main.cpp:321-330) and the viz node's panel (stereo_dnn_ros_viz_node.cpp:81-130), on the device.  Whatever an op-level call
-// can refuse is refused before anything is written: by the checks here, which precede the rectify launch, or by the front end, whose
-// limits are the back end's.
+// can refuse is refused before anything is written: by the checks here, which precede the decode and the rectify launch, or by the front
+// end, whose limits are the back end's.
 namespace {
 
 struct FrameJob {
@@ -337,6 +338,7 @@ struct FrameJob {
     const rtDepthCall* d = nullptr;                // rt_disparity_to_points in the place of rt_disparity_to_frame; c->disp optional
     const rtRectifyCall* r = nullptr;              // c's frames are raw: everything else runs on their rectified form
     const rtSpeckleCall* sp = nullptr;             // rt_disparity_speckle in network geometry; the back end then always gets a mask
+    const rtDecodeCall* dec = nullptr;             // c's frames are wire frames (mono, Bayer, YUV 4:2:2): everything else runs on their decoded form
     void* viz_rgb8 = nullptr;                      // the viz node's panel of c's frames and c->disp
     int64_t viz_step = 0;
     float max_disp = 0.f;
@@ -347,6 +349,7 @@ int run_frames(const std::string& fn, rtStereoNet* net, const FrameJob& j, rtStr
     const rtDepthCall* d = j.d;
     const rtRectifyCall* r = j.r;
     const rtSpeckleCall* sp = j.sp;
+    const rtDecodeCall* dec = j.dec;
     if (!net || !net->context || !c) return fail(fn + "null pointer");
     const auto wrong_size = [&fn](size_t got, size_t want, const char* type) {
         return fail(fn + "struct_bytes " + std::to_string(got) + " is not sizeof(" + type + ") = " + std::to_string(want));
@@ -355,6 +358,7 @@ int run_frames(const std::string& fn, rtStereoNet* net, const FrameJob& j, rtStr
     if (c->struct_bytes != sizeof(rtFrameCall)) return wrong_size(c->struct_bytes, sizeof(rtFrameCall), "rtFrameCall");
     if (d && d->struct_bytes != sizeof(rtDepthCall)) return wrong_size(d->struct_bytes, sizeof(rtDepthCall), "rtDepthCall");
     if (sp && sp->struct_bytes != sizeof(rtSpeckleCall)) return wrong_size(sp->struct_bytes, sizeof(rtSpeckleCall), "rtSpeckleCall");
+    if (dec && dec->struct_bytes != sizeof(rtDecodeCall)) return wrong_size(dec->struct_bytes, sizeof(rtDecodeCall), "rtDecodeCall");
     if (!c->left_u8 || !c->right_u8 || (!d && !c->disp)) return fail(fn + "null pointer");
     if (c->resize != RT_RESIZE_AREA_DOWN && c->resize != RT_RESIZE_CV_AREA) return fail(fn + "unknown resize " + std::to_string(c->resize));
     if (c->geometry != RT_GEOM_NET && c->geometry != RT_GEOM_FRAME) return fail(fn + "unknown geometry " + std::to_string(c->geometry));
@@ -402,23 +406,53 @@ int run_frames(const std::string& fn, rtStereoNet* net, const FrameJob& j, rtStr
         return RT_E_UNSUPPORTED;
     }
     const int H = net->height, W = net->width;
-    rtFrameCall rectified;
-    if (r) {
-        // What the front end and rt_rectify_frames_u8 would refuse, found here: behind the rectify launch an error could no longer
-        // write nothing.
-        const int bpp = c->encoding == RT_ENC_BGRA8 || c->encoding == RT_ENC_RGBA8 ? 4 : 3;
+    const int bpp = c->encoding == RT_ENC_BGRA8 || c->encoding == RT_ENC_RGBA8 ? 4 : 3;
+    rtFrameCall decoded, rectified;
+    if (r || dec) {
+        // What the front end, rt_decode_frames_u8 and rt_rectify_frames_u8 would refuse, found here: behind the first of these launches an
+        // error could no longer write nothing.  The frames the caller passes are wire frames with `dec`, and their step is held against
+        // the wire pixel.
+        if (dec && (dec->wire_encoding < RT_WIRE_MONO8 || dec->wire_encoding > RT_WIRE_YUV422_YUY2))
+            return fail(fn + "unknown wire encoding " + std::to_string(dec->wire_encoding));
+        const int in_bpp = !dec ? bpp : dec->wire_encoding == RT_WIRE_MONO16 || dec->wire_encoding >= RT_WIRE_YUV422 ? 2 : 1;
         if (c->src_h < 1 || c->src_w < 1 || c->src_h > (1 << 24) || c->src_w > (1 << 24) || (int64_t)c->src_h * c->src_w >= ((int64_t)1 << 31) ||
             batch > 32767)
             return fail(fn + "bad dims");
-        if (c->src_step < (int64_t)c->src_w * bpp)
+        if (c->src_step < (int64_t)c->src_w * in_bpp)
             return fail(fn + "row step " + std::to_string(c->src_step) + " is shorter than " + std::to_string(c->src_w) + " pixels of " +
-                        std::to_string(bpp) + " bytes");
+                        std::to_string(in_bpp) + " bytes");
         const bool down = H <= c->src_h && W <= c->src_w;
         if (c->resize == RT_RESIZE_AREA_DOWN && !down)
             return fail(fn + "INTER_AREA up-scaling (" + std::to_string(c->src_w) + "x" + std::to_string(c->src_h) + " -> " + std::to_string(W) + "x" +
                         std::to_string(H) + ") is not implemented by RT_RESIZE_AREA_DOWN");
         if ((float)c->src_w / W > 6.f || (float)c->src_h / H > 6.f || (float)W / c->src_w > 6.f || (float)H / c->src_h > 6.f)
             return fail(fn + "scale factors outside [1/6, 6] are not implemented");
+    }
+    const size_t dense = (size_t)net->max_batch * c->src_h * c->src_w * bpp;      // frames of the net's own, decoded or rectified
+    if (dec) {
+        if (!dec->left_color_u8 != !dec->right_color_u8) return fail(fn + "left_color_u8 and right_color_u8: both or neither");
+        if (dec->left_color_u8 ? dec->color_step < (int64_t)c->src_w * bpp : dec->color_step != 0)
+            return fail(fn + "color_step " + std::to_string(dec->color_step) + (dec->left_color_u8 ? " is shorter than a row" : " without buffers"));
+        if (dec->left_color_u8) {
+            for (const void* p : {dec->left_color_u8, dec->right_color_u8}) {
+                if (p == c->left_u8 || p == c->right_u8) return fail(fn + "a colour buffer must not be a wire buffer");
+                if (r && (p == r->left_rect_u8 || p == r->right_rect_u8)) return fail(fn + "a colour buffer must not be a rectified buffer");
+            }
+        }
+        decoded = *c;
+        if (dec->left_color_u8) {
+            decoded.left_u8 = dec->left_color_u8;
+            decoded.right_u8 = dec->right_color_u8;
+            decoded.src_step = dec->color_step;
+        } else {
+            if (!net->color[0].grow(dense) || !net->color[1].grow(dense)) return fail(fn + rt_last_error_string());
+            decoded.left_u8 = net->color[0].p;
+            decoded.right_u8 = net->color[1].p;
+            decoded.src_step = (int64_t)c->src_w * bpp;
+        }
+    }
+    if (r) {
+        const rtFrameCall* raw = dec ? &decoded : c;       // what the rectify launch reads
         if (!r->left_rect_u8 != !r->right_rect_u8) return fail(fn + "left_rect_u8 and right_rect_u8: both or neither");
         if (r->left_rect_u8 ? r->rect_step < (int64_t)c->src_w * bpp : r->rect_step != 0)
             return fail(fn + "rect_step " + std::to_string(r->rect_step) + (r->left_rect_u8 ? " is shorter than a row" : " without buffers"));
@@ -427,19 +461,26 @@ int run_frames(const std::string& fn, rtStereoNet* net, const FrameJob& j, rtStr
             for (size_t i = 0; i < sizeof(rtRectifyCamera) / sizeof(double); i++)
                 if (!std::isfinite(v[i])) return fail(fn + "every field of a camera must be finite");
         }
-        if (r->left_rect_u8 == c->left_u8 || r->right_rect_u8 == c->right_u8) return fail(fn + "a rectified buffer must not be the raw one");
-        rectified = *c;
+        if (r->left_rect_u8 == raw->left_u8 || r->right_rect_u8 == raw->right_u8) return fail(fn + "a rectified buffer must not be the raw one");
+        rectified = *raw;
         if (r->left_rect_u8) {
             rectified.left_u8 = r->left_rect_u8;
             rectified.right_u8 = r->right_rect_u8;
             rectified.src_step = r->rect_step;
         } else {
-            const size_t need = (size_t)net->max_batch * c->src_h * c->src_w * bpp;
-            if (!net->rect[0].grow(need) || !net->rect[1].grow(need)) return fail(fn + rt_last_error_string());
+            if (!net->rect[0].grow(dense) || !net->rect[1].grow(dense)) return fail(fn + rt_last_error_string());
             rectified.left_u8 = net->rect[0].p;
             rectified.right_u8 = net->rect[1].p;
             rectified.src_step = (int64_t)c->src_w * bpp;
         }
+    }
+    if (dec) {                                             // the first launch: whatever it refuses, nothing has been written
+        if (rt_decode_frames_u8(c->left_u8, c->right_u8, c->src_h, c->src_w, c->src_step, dec->wire_encoding, const_cast<void*>(decoded.left_u8),
+                                const_cast<void*>(decoded.right_u8), decoded.src_step, c->encoding, batch, stream) != 0)
+            return fail(fn + rt_last_error_string());
+        c = &decoded;
+    }
+    if (r) {
         if (rt_rectify_frames_u8(c->left_u8, c->right_u8, c->src_h, c->src_w, c->src_step, c->encoding, &r->left, &r->right,
                                  const_cast<void*>(rectified.left_u8), const_cast<void*>(rectified.right_u8), c->src_h, c->src_w, rectified.src_step,
                                  batch, stream) != 0)
@@ -448,7 +489,7 @@ int run_frames(const std::string& fn, rtStereoNet* net, const FrameJob& j, rtStr
     }
     // RT_RESIZE_AREA_DOWN into RT_GEOM_NET is what rt_net_execute_frames / _lr do, whichever entry asks: from here on an error reports
     // under their names (a front end's refusal reads the same through every entry)
-    const std::string as = d || c->resize != RT_RESIZE_AREA_DOWN || frame ? fn : check ? "rt_net_execute_frames_lr: " : "rt_net_execute_frames: ";
+    const std::string as = d || dec || c->resize != RT_RESIZE_AREA_DOWN || frame ? fn : check ? "rt_net_execute_frames_lr: " : "rt_net_execute_frames: ";
     const int64_t pixels = (int64_t)H * W;
     const size_t plane = (size_t)net->max_batch * pixels;
     if (!net->frame_in[0].ensure(3 * plane * sizeof(float)) || !net->frame_in[1].ensure(3 * plane * sizeof(float)) ||
@@ -608,6 +649,19 @@ extern "C" int rt_net_execute_frames_raw(rtStereoNet* net, const rtFrameCall* ca
 extern "C" int rt_net_execute_frames_filtered(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out, const rtRectifyCall* rect,
                                               const rtSpeckleCall* speckle, rtStream stream) {
     return run_call(net, call, out, rect, speckle, stream);
+}
+
+// ... from what the camera really sends: one rt_decode_frames_u8 launch in front, everything else on its output
+extern "C" int rt_net_execute_frames_camera(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out, const rtRectifyCall* rect,
+                                            const rtSpeckleCall* speckle, const rtDecodeCall* decode, rtStream stream) {
+    if (!decode) return run_call(net, call, out, rect, speckle, stream);
+    FrameJob j;
+    j.c = call;
+    j.d = out;
+    j.r = rect;
+    j.sp = speckle;
+    j.dec = decode;
+    return run_frames("rt_net_execute_frames_camera: ", net, j, stream);
 }
 
 extern "C" int rt_net_profile(rtStereoNet* net, const void* left, const void* right, void* disp, int batch, char* buf,

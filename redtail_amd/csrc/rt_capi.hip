@@ -29,6 +29,7 @@
 #include "kernels/deconv3d_small.hip.h"
 #include "kernels/imgproc.hip.h"
 #include "kernels/rectify.hip.h"
+#include "kernels/decode.hip.h"
 #include "kernels/speckle.hip.h"
 #include "kernels/conv_f16.hip.h"
 #include "kernels/conv_f16_first.hip.h"
@@ -831,6 +832,52 @@ extern "C" int rt_rectify_maps(const rtRectifyCamera* cam, int dst_h, int dst_w,
     hipLaunchKernelGGL(rt::rectify_maps_kernel, grid, dim3(rt::kFramesCols * rt::kFramesRows), 0, S(s), c, static_cast<float*>(map_x),
                        static_cast<float*>(map_y), dst_h, dst_w);
     RT_LAUNCH_CHECK("rectify_maps_kernel");
+    return 0;
+}
+
+// What the camera really sends -> the colour frames of the frame path (kernels/decode.hip.h): mono, Bayer, YUV 4:2:2.  As rectify_launch,
+// the dword forms are taken when every base and step is a multiple of 4 and the byte forms otherwise.
+extern "C" int rt_decode_frames_u8(const void* left_wire, const void* right_wire, int h, int w, int64_t wire_step, int wire_encoding,
+                                   void* left_u8, void* right_u8, int64_t dst_step, int dst_encoding, int batch, rtStream s) {
+    const char* fn = "rt_decode_frames_u8";
+    RT_REQUIRE(left_wire && right_wire && left_u8 && right_u8, "%s: null pointer", fn);
+    RT_REQUIRE(wire_encoding >= RT_WIRE_MONO8 && wire_encoding <= RT_WIRE_YUV422_YUY2, "%s: unknown wire encoding %d", fn, wire_encoding);
+    RT_REQUIRE(dst_encoding >= RT_ENC_BGR8 && dst_encoding <= RT_ENC_RGBA8, "%s: unknown encoding %d", fn, dst_encoding);
+    RT_REQUIRE(h > 0 && w > 0 && batch > 0 && batch <= 32767 && h <= 4 * 65535 && w <= (1 << 24), "%s: bad dims", fn);
+    const bool bayer = wire_encoding >= RT_WIRE_BAYER_RGGB8 && wire_encoding <= RT_WIRE_BAYER_GRBG8;
+    const bool yuv = wire_encoding == RT_WIRE_YUV422 || wire_encoding == RT_WIRE_YUV422_YUY2;
+    RT_REQUIRE(!bayer || (h >= 2 && w >= 2), "%s: a Bayer mosaic needs at least 2 x 2 pixels, not %d x %d", fn, w, h);
+    RT_REQUIRE(!yuv || w % 2 == 0, "%s: YUV 4:2:2 needs an even width, not %d", fn, w);
+    const int wire_bpp = yuv || wire_encoding == RT_WIRE_MONO16 ? 2 : 1;
+    const int bpp = dst_encoding == RT_ENC_BGRA8 || dst_encoding == RT_ENC_RGBA8 ? 4 : 3;
+    RT_REQUIRE(wire_step >= (int64_t)w * wire_bpp, "%s: row step %lld is shorter than %d pixels of %d bytes", fn, (long long)wire_step, w, wire_bpp);
+    RT_REQUIRE(dst_step >= (int64_t)w * bpp, "%s: destination row step %lld is shorter than %d pixels of %d bytes", fn, (long long)dst_step, w, bpp);
+    RT_REQUIRE(left_u8 != left_wire && left_u8 != right_wire && right_u8 != left_wire && right_u8 != right_wire && left_u8 != right_u8,
+               "%s: source and destination must not overlap", fn);
+    rt::DecodeArgs a{};
+    a.left = static_cast<const unsigned char*>(left_wire); a.right = static_cast<const unsigned char*>(right_wire);
+    a.dleft = static_cast<unsigned char*>(left_u8); a.dright = static_cast<unsigned char*>(right_u8);
+    a.h = h; a.w = w; a.step = wire_step; a.dstep = dst_step; a.batch = batch;
+    a.rgb = dst_encoding == RT_ENC_RGB8 || dst_encoding == RT_ENC_RGBA8;
+    a.r_row = wire_encoding == RT_WIRE_BAYER_BGGR8 || wire_encoding == RT_WIRE_BAYER_GBRG8;       // rggb: R at (0,0), grbg: (0,1), gbrg: (1,0), bggr: (1,1)
+    a.r_col = wire_encoding == RT_WIRE_BAYER_BGGR8 || wire_encoding == RT_WIRE_BAYER_GRBG8;
+    a.yuy2 = wire_encoding == RT_WIRE_YUV422_YUY2;
+    const bool dword = ((reinterpret_cast<uintptr_t>(left_wire) | reinterpret_cast<uintptr_t>(right_wire) | reinterpret_cast<uintptr_t>(left_u8) |
+                         reinterpret_cast<uintptr_t>(right_u8) | (uintptr_t)wire_step | (uintptr_t)dst_step) & 3) == 0;
+    const int rows = rt::kFramesRows * (bayer ? 2 : 1);
+    const dim3 grid((unsigned)rt::cdiv(w, rt::kFramesCols * rt::kDecodeRun), (unsigned)rt::cdiv(h, rows), (unsigned)(2 * batch));
+    const dim3 block(rt::kFramesCols * rt::kFramesRows);
+    auto launch = [&](auto k3, auto k3d, auto k4, auto k4d) {
+        hipLaunchKernelGGL(bpp == 3 ? (dword ? k3d : k3) : (dword ? k4d : k4), grid, block, 0, S(s), a);
+    };
+#define RT_DECODE_FORMS(mode) rt::decode_frames_kernel<mode, 3, false>, rt::decode_frames_kernel<mode, 3, true>, \
+                              rt::decode_frames_kernel<mode, 4, false>, rt::decode_frames_kernel<mode, 4, true>
+    if (bayer) launch(RT_DECODE_FORMS(rt::kDecodeBayer));
+    else if (yuv) launch(RT_DECODE_FORMS(rt::kDecodeYuv));
+    else if (wire_encoding == RT_WIRE_MONO16) launch(RT_DECODE_FORMS(rt::kDecodeMono16));
+    else launch(RT_DECODE_FORMS(rt::kDecodeMono8));
+#undef RT_DECODE_FORMS
+    RT_LAUNCH_CHECK("decode_frames_kernel");
     return 0;
 }
 
