@@ -329,6 +329,53 @@ int rt_disparity_to_points(const void* disp_px, const void* mask_u8, int batch, 
                            int encoding, void* disp_out, int disp_kind, void* out_mask_u8, void* valid_count, void* depth, int depth_kind,
                            void* points, void* points_compact, void* count, void* workspace, size_t workspace_bytes, rtStream stream);
 
+/* ---- the cloud on a voxel grid (no counterpart in the reference; pcl::VoxelGrid, the node behind stereo_image_proc/point_cloud2) --------- */
+/* A box of dims[0] x dims[1] x dims[2] cells of leaf[0] x leaf[1] x leaf[2] metres whose corner is `origin`, axes x, y, z of the camera
+ * frame the cloud is in. */
+typedef struct rtVoxelGrid { float origin[3]; float leaf[3]; int dims[3]; } rtVoxelGrid;   /* x, y, z; camera frame, metres */
+/* One record per occupied cell of the grid: the centroid of the cell's points and their mean colour.  What a planner, an octomap or a
+ * collision checker takes instead of one point per pixel.
+ * points:  (batch, capacity) records of 16 bytes {float x, y, z; uint32 rgb} as rt_disparity_to_points writes them; image n starts at record
+ *          n * capacity.  count == NULL: all `capacity` records of an image are read (the organised cloud, whose invalid pixels are NaN).
+ *          Otherwise count is `batch` uint64 on the device and only the first min(count[n], capacity) records of image n are read
+ *          (points_compact with its count).
+ * CELL of a point, per axis a, all fp32, every operation rounded on its own, the division IEEE, nothing contracted:
+ *   t_a = (p_a - origin_a) / leaf_a
+ *   the point is IN THE GRID iff for all three axes  t_a >= 0.f && t_a < (float)dims_a   (a NaN fails: invalid pixels drop out; so does
+ *   an infinity)
+ *   i_a = (int)floorf(t_a);   cell = (i_z * dims_y + i_y) * dims_x + i_x
+ *   f_a = t_a - floorf(t_a)   (exact);   q_a = (uint32)(f_a * 65536.f)   (truncated; in [0, 65535])
+ * Per VOXEL -- a cell with at least one point of image n -- integer sums, so their order does not matter:
+ *   N = number of points;   S_a = sum of q_a;   R, G, B = sums of the colour bytes (rgb >> 16 & 255, rgb >> 8 & 255, rgb & 255)
+ * A voxel is EMITTED iff N >= min_points, as the record
+ *   g_a = ((double)S_a / (double)N + 0.5) / 65536.0                                  in double
+ *   c_a = (origin_a + (float)i_a * leaf_a) + (float)g_a * leaf_a                     in fp32, each operation rounded on its own
+ *   rgb = r << 16 | g << 8 | b  with  r = (R + N / 2) / N  in integer arithmetic, g and b likewise
+ * (the centroid from 16-bit offsets inside the cell: it differs from the mean of the floats by less than leaf_a / 131072 plus fp32
+ * rounding).
+ * voxels:  the emitted voxels of image n IN ASCENDING cell from byte n * out_capacity * 16 on, {float c_x, c_y, c_z; uint32 rgb}; at most
+ *          out_capacity records are written, the first ones in that order; bytes behind the last record are not touched.
+ * out_count:    `batch` uint64 on the device, zeroed by the entry, required: the number of emitted voxels of image n whether or not they
+ *               fitted (out_count[n] > out_capacity: the cloud was truncated).
+ * out_cell_u32, out_n_u32: optional, laid out like voxels with 4 bytes per record: `cell` and N of each written record (an occupancy
+ *               grid's index; a weight).
+ * The result is a pure function of the SET of points of each image: permuting an image's records changes no bit, the compact and the
+ * organised cloud of one rt_disparity_to_points call give the same bytes, and every run is bit-identical, in whatever order the device ran
+ * the work.
+ * `workspace`: device memory of rt_voxel_workspace_bytes(batch, capacity, grid) bytes, 8-byte aligned, private to the stream until the
+ * launches have run; nothing depends on what it held.  Per image it is one bit and one prefix word per 32 cells, 44 bytes per slot with
+ * min(capacity, cells) slots, and the scans' block sums: a 2^27-cell grid costs 32 MiB and a memset of 16 MiB, whatever the cloud's size.
+ * Launches: mark, two for the scan, zero, accumulate, emit; two more with min_points > 1.
+ * Errors, found before anything is written: a null points, grid, voxels or out_count; batch < 1 or > 32767; capacity or out_capacity
+ * outside [1, 2^23] (2^23 keeps the colour sums inside 32 bits); a dims entry outside [1, 4096] or more than 2^27 cells; a leaf that is
+ * not finite and > 0; an origin that is not finite; min_points < 1; points or voxels off a 16-byte boundary (the counts: 8, out_cell_u32
+ * and out_n_u32: 4); a missing, short or misaligned workspace; any overlap of an output or the workspace with an input or with one
+ * another.  rt_voxel_workspace_bytes returns 0 for a batch, a capacity or a grid the op refuses. */
+size_t rt_voxel_workspace_bytes(int batch, int capacity, const rtVoxelGrid* grid);          /* 0 for what the op refuses */
+int rt_points_voxel_grid(const void* points, const void* count, int batch, int capacity, const rtVoxelGrid* grid, int min_points,
+                         void* voxels, int out_capacity, void* out_count, void* out_cell_u32, void* out_n_u32,
+                         void* workspace, size_t workspace_bytes, rtStream stream);
+
 /* ---- raw frames in: rectification (image_proc's stage in front of stereo_image_proc; the reference node subscribes to image_rect_color) -- */
 /* One camera of the rig, from its sensor_msgs/CameraInfo (all float64 there). */
 typedef struct rtRectifyCamera {

@@ -237,6 +237,36 @@ int rt_net_execute_frames_camera(rtStereoNet* net, const rtFrameCall* call, cons
                                  const rtRectifyCall* rect /* or NULL */, const rtSpeckleCall* speckle /* or NULL */,
                                  const rtDecodeCall* decode /* or NULL */, rtStream stream);
 
+/* What a planner can take: rt_net_execute_frames_camera with the cloud put on a voxel grid (rt_stereo.h: rt_points_voxel_grid, where cells,
+ * sums, the emitted record and its order are defined; pcl::VoxelGrid, the node behind stereo_image_proc/point_cloud2).
+ *   voxel == NULL: rt_net_execute_frames_camera on the same arguments, refusals and error texts included.
+ *   voxel != NULL: `out` is required -- it carries the camera and the depth range -- and may have every output pointer NULL: "no output
+ *                  requested" is satisfied by the voxels.  The sequence is the existing one with ONE
+ *                  rt_points_voxel_grid(grid, min_points) behind rt_disparity_to_points.  Its input cloud is the caller's out->points
+ *                  (read with count == NULL) or, failing that, out->points_compact with out->count, where one was asked for; otherwise an
+ *                  organised cloud in a buffer the net owns, made on first use and regrown when a larger frame arrives.  The choice cannot
+ *                  be observed: the op's result is a function of the set of valid points, which is the same in all three.
+ *                  voxels / capacity / count / cell_u32 / n_u32 are the op's voxels / out_capacity / out_count / out_cell_u32 /
+ *                  out_n_u32, capacity per image.
+ * Composition is the definition: every output is bit-identical to rt_net_execute_frames_camera followed by rt_points_voxel_grid by hand.
+ * The voxel workspace is a buffer the net owns, grown on demand.  The op runs outside the engine's graph, so every pointer may rotate in
+ * graph mode; stream == NULL: synchronous.  All checks of all six structs are made before the first launch, so an error writes nothing:
+ * whatever the wrapped call refuses, whatever rt_points_voxel_grid refuses (a frame of more than 2^23 pixels included), a wrong
+ * struct_bytes, a NULL `out`, voxel buffers that overlap the cloud they are made from. */
+typedef struct rtVoxelCall {
+    size_t struct_bytes;       /* sizeof(rtVoxelCall) */
+    rtVoxelGrid grid;
+    int min_points;
+    void* voxels;              /* rt_points_voxel_grid's outputs; capacity per image */
+    int capacity;
+    void* count;
+    void* cell_u32;            /* optional */
+    void* n_u32;               /* optional */
+} rtVoxelCall;
+int rt_net_execute_frames_voxels(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out, const rtRectifyCall* rect /* or NULL */,
+                                 const rtSpeckleCall* speckle /* or NULL */, const rtDecodeCall* decode /* or NULL */,
+                                 const rtVoxelCall* voxel /* or NULL */, rtStream stream);
+
 /* Per-launch timing through nvinfer1::IProfiler (single stream, one event pair per launch):
  * writes "name<TAB>milliseconds\n" lines into buf.  Returns 0 or an error. */
 int rt_net_profile(rtStereoNet* net, const void* left, const void* right, void* disp, int batch, char* buf,

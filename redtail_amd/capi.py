@@ -69,6 +69,16 @@ class RectifyCamera(ctypes.Structure):
         return cam
 
 
+class VoxelGrid(ctypes.Structure):
+    """rtVoxelGrid (include/rt_stereo.h): origin, leaf and dims per axis x, y, z; camera frame, metres"""
+    _fields_ = [("origin", c_float * 3), ("leaf", c_float * 3), ("dims", c_int * 3)]
+
+    @classmethod
+    def make(cls, origin, leaf, dims):
+        leaf = (leaf,) * 3 if isinstance(leaf, (int, float)) else leaf
+        return cls((c_float * 3)(*origin), (c_float * 3)(*leaf), (c_int * 3)(*dims))
+
+
 class Conv3dDesc(ctypes.Structure):
     _fields_ = [("C", c_int), ("K", c_int), ("D", c_int), ("H", c_int), ("W", c_int), ("kernel", c_int * 3),
                 ("stride", c_int * 3), ("pad_start", c_int * 3), ("pad_end", c_int * 3), ("act", c_int),
@@ -138,6 +148,9 @@ KERNEL_SYMBOLS = {
                                        c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_size_t, c_void_p]),
     "rt_speckle_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "rt_voxel_workspace_bytes": (c_size_t, [c_int, c_int, c_void_p]),
+    "rt_points_voxel_grid": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_size_t, c_void_p]),
     "rt_disparity_speckle": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                      c_void_p]),
     "rt_rectify_camera_from_info": (c_int, [POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double), POINTER(c_double),
@@ -362,6 +375,23 @@ class KernelLib:
         self.check(self.lib.rt_disparity_speckle(_ptr(disp_px), _ptr(mask), batch, h, w, max_size, max_diff_px, _ptr(out), _ptr(out_mask),
                                                  _ptr(valid_count), _ptr(workspace), workspace_bytes, stream), "rt_disparity_speckle")
 
+    def voxel_workspace_bytes(self, batch, capacity, grid):
+        """bytes of device workspace points_voxel_grid needs (0 for a batch, a capacity or a grid it refuses)"""
+        return self.lib.rt_voxel_workspace_bytes(batch, capacity, ctypes.byref(grid) if grid is not None else None)
+
+    def points_voxel_grid(self, points, batch, capacity, grid, voxels, out_capacity, out_count, count=None, min_points=1, out_cell=None,
+                          out_n=None, workspace=None, workspace_bytes=None, stream=None):
+        """pcl::VoxelGrid on the device: (N, capacity) x 16-byte records {x, y, z, rgb} -- the organised cloud (count=None, NaNs drop out) or
+        the compact cloud with its N uint64 `count` -- onto `grid` (VoxelGrid).  voxels: (N, out_capacity) x 16 bytes, the centroid and mean
+        colour of every cell with >= min_points points in ascending cell index; out_count: N uint64, the number emitted (> out_capacity:
+        truncated); out_cell / out_n: (N, out_capacity) uint32, cell index and point count per record.  workspace: voxel_workspace_bytes of
+        device memory.  The result does not depend on the order of the records."""
+        if workspace_bytes is None:
+            workspace_bytes = 0 if workspace is None else (workspace.numel() * workspace.element_size() if hasattr(workspace, "numel") else workspace.nbytes)
+        self.check(self.lib.rt_points_voxel_grid(_ptr(points), _ptr(count), batch, capacity, ctypes.byref(grid) if grid is not None else None,
+                                                 min_points, _ptr(voxels), out_capacity, _ptr(out_count), _ptr(out_cell), _ptr(out_n),
+                                                 _ptr(workspace), workspace_bytes, stream), "rt_points_voxel_grid")
+
     def corr_softargmax_pitched(self, l, r, out, batch, C, H, W, D, is_min, in_pitch, out_pitch, out_bstride=0,
                                 dtype=RT_F32, stream=None):
         self.check(self.lib.rt_corr_softargmax_pitched(_ptr(l), _ptr(r), _ptr(out), batch, C, H, W, D, int(is_min),
@@ -575,6 +605,7 @@ NET_SYMBOLS = {
     "rt_net_execute_frames_raw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rt_net_execute_frames_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rt_net_execute_frames_camera": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rt_net_execute_frames_voxels": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rt_net_profile": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_char_p, c_size_t]),
     "rt_net_num_layers": (c_int, [c_void_p]),
     "rt_net_num_launches": (c_int, [c_void_p]),
@@ -628,6 +659,12 @@ class DecodeCall(ctypes.Structure):
     """rtDecodeCall (include/rt_stereo_net.h)"""
     _fields_ = [("struct_bytes", c_size_t), ("wire_encoding", c_int), ("left_color_u8", c_void_p), ("right_color_u8", c_void_p),
                 ("color_step", c_int64)]
+
+
+class VoxelCall(ctypes.Structure):
+    """rtVoxelCall (include/rt_stereo_net.h)"""
+    _fields_ = [("struct_bytes", c_size_t), ("grid", VoxelGrid), ("min_points", c_int), ("voxels", c_void_p), ("capacity", c_int),
+                ("count", c_void_p), ("cell_u32", c_void_p), ("n_u32", c_void_p)]
 
 
 def pack_weights(weights, fp16=False):
@@ -946,6 +983,63 @@ class StereoNet:
                                              _ptr(left_color), _ptr(right_color), color_step))
         self.netlib.check(self.netlib.lib.rt_net_execute_frames_camera(self.handle, ctypes.byref(call), out, rect, speckle, decode, stream),
                           "rt_net_execute_frames_camera")
+
+    def execute_frames_voxels(self, left_u8, right_u8, encoding, grid=None, min_points=1, voxels=None, voxel_capacity=None, voxel_count=None,
+                              voxel_cell=None, voxel_n=None, voxel_struct_bytes=None, speckle_size=None, speckle_range=1.0, rect_left=None,
+                              rect_right=None, camera=None, disp=None, kind=RT_DISP_PIXELS_F32, geometry=RT_GEOM_FRAME, resize=RT_RESIZE_CV_AREA,
+                              max_diff_px=-1.0, mask=None, valid_count=None, min_depth=0.0, max_depth=float("inf"), depth=None,
+                              depth_kind=RT_DEPTH_M_F32, points=None, points_compact=None, count=None, batch=1, stream=None, src_step=None,
+                              src_w=None, struct_bytes=None, depth_struct_bytes=None, no_depth_call=False, left_rect=None, right_rect=None,
+                              rect_step=None, rect_struct_bytes=None, speckle_struct_bytes=None, wire_encoding=None, left_color=None,
+                              right_color=None, color_step=None, decode_struct_bytes=None):
+        """rt_net_execute_frames_voxels: execute_frames_filtered with the same keywords (and, wire_encoding given, execute_frames_camera's:
+        left_u8 / right_u8 are then (N, H, step) wire frames), plus one points_voxel_grid(grid, min_points) behind the cloud: voxels
+        (N, voxel_capacity) x 16 bytes -- voxel_capacity defaulting to the buffer's records per image --, voxel_count N uint64, voxel_cell /
+        voxel_n (N, voxel_capacity) uint32.  No cloud output need be asked for.  grid=None: no voxel call, the wrapped call itself."""
+        strides = lambda t: tuple(t.stride()) if hasattr(t, "data_ptr") else tuple(t.strides)
+        if wire_encoding is None:
+            h, w, step = self._frame_geometry("rt_net_execute_frames_voxels", left_u8, right_u8, encoding, batch, src_step, src_w)
+        else:
+            shape, st = tuple(left_u8.shape), strides(left_u8)
+            if len(shape) != 3 or tuple(right_u8.shape) != shape or strides(right_u8) != st or st[2] != 1:
+                raise ValueError("wire frames must be two (N,H,step) uint8 batches of the same shape, rows of contiguous bytes")
+            if shape[0] < batch or (batch > 1 and st[0] != shape[1] * st[1]):
+                raise ValueError("frame batch must hold %d frames of %d rows of %d bytes back to back" % (batch, shape[1], st[1]))
+            h, step = shape[1], st[1] if src_step is None else src_step
+            w = src_w if src_w is not None else shape[2] // WIRE_BYTES.get(wire_encoding, 1)
+        call = FrameCall(ctypes.sizeof(FrameCall) if struct_bytes is None else struct_bytes, _ptr(left_u8), _ptr(right_u8), h, w, step, encoding,
+                         resize, _ptr(disp), kind, geometry, max_diff_px, _ptr(mask), _ptr(valid_count), batch)
+        out = None
+        if not no_depth_call:
+            out = ctypes.byref(DepthCall(ctypes.sizeof(DepthCall) if depth_struct_bytes is None else depth_struct_bytes,
+                                         camera if camera is not None else StereoCamera(), min_depth, max_depth, _ptr(depth), depth_kind,
+                                         _ptr(points), _ptr(points_compact), _ptr(count)))
+        rect = None
+        if rect_left is not None or rect_right is not None:
+            if rect_step is None:
+                given = left_rect if left_rect is not None else right_rect
+                rect_step = 0 if given is None else strides(given)[1]
+            rect = ctypes.byref(RectifyCall(ctypes.sizeof(RectifyCall) if rect_struct_bytes is None else rect_struct_bytes, rect_left, rect_right,
+                                            _ptr(left_rect), _ptr(right_rect), rect_step))
+        speckle = None
+        if speckle_size is not None:
+            speckle = ctypes.byref(SpeckleCall(ctypes.sizeof(SpeckleCall) if speckle_struct_bytes is None else speckle_struct_bytes, speckle_size,
+                                               speckle_range))
+        decode = None
+        if wire_encoding is not None:
+            if color_step is None:
+                given = left_color if left_color is not None else right_color
+                color_step = 0 if given is None else strides(given)[1]
+            decode = ctypes.byref(DecodeCall(ctypes.sizeof(DecodeCall) if decode_struct_bytes is None else decode_struct_bytes, wire_encoding,
+                                             _ptr(left_color), _ptr(right_color), color_step))
+        voxel = None
+        if grid is not None:
+            if voxel_capacity is None:
+                voxel_capacity = 0 if voxels is None else int(voxels.shape[1])
+            voxel = ctypes.byref(VoxelCall(ctypes.sizeof(VoxelCall) if voxel_struct_bytes is None else voxel_struct_bytes, grid, min_points,
+                                           _ptr(voxels), voxel_capacity, _ptr(voxel_count), _ptr(voxel_cell), _ptr(voxel_n)))
+        self.netlib.check(self.netlib.lib.rt_net_execute_frames_voxels(self.handle, ctypes.byref(call), out, rect, speckle, decode, voxel, stream),
+                          "rt_net_execute_frames_voxels")
 
     def set_debug(self, on=True):
         """IExecutionContext::setDebugSync: synchronise every launch and range-check the input of every fp16-pipe convolution"""

@@ -89,6 +89,7 @@ struct rtStereoNet {
     DeviceBuffer rect[2];                         // raw frames without caller buffers: dense rectified frames, grown on demand
     DeviceBuffer color[2];                        // wire frames without caller buffers: dense decoded frames, grown on demand
     DeviceBuffer speckle_ws;                      // with a filter: rt_disparity_speckle's workspace
+    DeviceBuffer voxel_cloud, voxel_ws;           // with a voxel grid: the organised cloud where the caller asks for none, and rt_points_voxel_grid's workspace; grown on demand
     ~rtStereoNet() {                              // (the buffers go after the engine that may still name them)
         if (context) context->destroy();
         if (engine) engine->destroy();
@@ -318,12 +319,12 @@ extern "C" int rt_net_execute(rtStereoNet* net, const void* left, const void* ri
 }
 
 // ---- the camera-frame path ---------------------------------------------------------------------------------------------------------------
-// The eight rt_net_execute_frames* entries fill a FrameJob and make the checks that are theirs alone; run_frames does everything else, once:
+// The nine rt_net_execute_frames* entries fill a FrameJob and make the checks that are theirs alone; run_frames does everything else, once:
 //   validate everything -> make or grow the net's buffers -> [rt_rectify_frames_u8] -> rt_preprocess_frames_u8 / _u8_lr / _u8_cv
 //   -> one engine pass at batch (2 * batch with a check) on the net's three bindings
 //   -> [rt_lr_consistency | rt_disparity_scale] -> [rt_disparity_speckle]
 //   -> one back end: network geometry (copy, scale or 16-bit; with a check rt_lr_consistency is the back end), rt_disparity_to_frame or
-//      rt_disparity_to_points
+//      rt_disparity_to_points -> [rt_points_voxel_grid]
 //   -> [rt_viz_mosaic_u8] -> one rt_stream_sync when there is no stream.
 // It is the ROS node's computeOutputs (stereo_dnn_ros_node.cpp:60-103) after the H2D copy of the raw frames, the sample app's result path
 // (sample_app/main.cpp:321-330) and the viz node's panel (stereo_dnn_ros_viz_node.cpp:81-130), on the device.  Whatever an op-level call
@@ -339,6 +340,7 @@ struct FrameJob {
     const rtRectifyCall* r = nullptr;              // c's frames are raw: everything else runs on their rectified form
     const rtSpeckleCall* sp = nullptr;             // rt_disparity_speckle in network geometry; the back end then always gets a mask
     const rtDecodeCall* dec = nullptr;             // c's frames are wire frames (mono, Bayer, YUV 4:2:2): everything else runs on their decoded form
+    const rtVoxelCall* vx = nullptr;               // rt_points_voxel_grid behind rt_disparity_to_points; d required, its outputs optional
     void* viz_rgb8 = nullptr;                      // the viz node's panel of c's frames and c->disp
     int64_t viz_step = 0;
     float max_disp = 0.f;
@@ -350,7 +352,8 @@ int run_frames(const std::string& fn, rtStereoNet* net, const FrameJob& j, rtStr
     const rtRectifyCall* r = j.r;
     const rtSpeckleCall* sp = j.sp;
     const rtDecodeCall* dec = j.dec;
-    if (!net || !net->context || !c) return fail(fn + "null pointer");
+    const rtVoxelCall* vx = j.vx;
+    if (!net || !net->context || !c || (vx && !d)) return fail(fn + "null pointer");
     const auto wrong_size = [&fn](size_t got, size_t want, const char* type) {
         return fail(fn + "struct_bytes " + std::to_string(got) + " is not sizeof(" + type + ") = " + std::to_string(want));
     };
@@ -359,6 +362,7 @@ int run_frames(const std::string& fn, rtStereoNet* net, const FrameJob& j, rtStr
     if (d && d->struct_bytes != sizeof(rtDepthCall)) return wrong_size(d->struct_bytes, sizeof(rtDepthCall), "rtDepthCall");
     if (sp && sp->struct_bytes != sizeof(rtSpeckleCall)) return wrong_size(sp->struct_bytes, sizeof(rtSpeckleCall), "rtSpeckleCall");
     if (dec && dec->struct_bytes != sizeof(rtDecodeCall)) return wrong_size(dec->struct_bytes, sizeof(rtDecodeCall), "rtDecodeCall");
+    if (vx && vx->struct_bytes != sizeof(rtVoxelCall)) return wrong_size(vx->struct_bytes, sizeof(rtVoxelCall), "rtVoxelCall");
     if (!c->left_u8 || !c->right_u8 || (!d && !c->disp)) return fail(fn + "null pointer");
     if (c->resize != RT_RESIZE_AREA_DOWN && c->resize != RT_RESIZE_CV_AREA) return fail(fn + "unknown resize " + std::to_string(c->resize));
     if (c->geometry != RT_GEOM_NET && c->geometry != RT_GEOM_FRAME) return fail(fn + "unknown geometry " + std::to_string(c->geometry));
@@ -371,7 +375,7 @@ int run_frames(const std::string& fn, rtStereoNet* net, const FrameJob& j, rtStr
             fail(fn + "depth and cloud exist in the camera's own geometry only: RT_GEOM_NET is not supported, use RT_GEOM_FRAME");
             return RT_E_UNSUPPORTED;
         }
-        if (!d->depth && !d->points && !d->points_compact && !d->count && !c->disp) return fail(fn + "no output requested");
+        if (!d->depth && !d->points && !d->points_compact && !d->count && !c->disp && !vx) return fail(fn + "no output requested");
         if (d->depth && d->depth_kind != RT_DEPTH_M_F32 && d->depth_kind != RT_DEPTH_MM_U16)
             return fail(fn + "unknown depth_kind " + std::to_string(d->depth_kind));
         if (!(k.fx > 0.f && k.fx <= kMax && k.fy > 0.f && k.fy <= kMax && k.baseline > 0.f && k.baseline <= kMax))
@@ -404,6 +408,34 @@ int run_frames(const std::string& fn, rtStereoNet* net, const FrameJob& j, rtStr
     if (frame && (!d || c->disp) && c->disp_kind == RT_DISP_NET) {
         fail(fn + "RT_GEOM_FRAME needs a disparity in pixels (RT_DISP_PIXELS_F32 / RT_DISP_KITTI_U16), not RT_DISP_NET");
         return RT_E_UNSUPPORTED;
+    }
+    if (vx) {                                          // what only rt_points_voxel_grid can refuse
+        if (!vx->voxels || !vx->count) return fail(fn + "null pointer");
+        if (c->src_h < 1 || c->src_w < 1) return fail(fn + "bad dims");
+        const int64_t records = (int64_t)c->src_h * c->src_w;
+        if (records > (1 << 23)) return fail(fn + "a frame of more than 2^23 pixels is beyond the voxel grid's limits");
+        if (vx->capacity < 1 || vx->capacity > (1 << 23)) return fail(fn + "voxel capacity " + std::to_string(vx->capacity) + " outside [1, 2^23]");
+        if (vx->min_points < 1) return fail(fn + "min_points must be >= 1");
+        if ((reinterpret_cast<uintptr_t>(vx->voxels) & 15) != 0) return fail(fn + "a cloud must start on a 16-byte boundary");
+        if ((reinterpret_cast<uintptr_t>(vx->count) & 7) != 0 || ((reinterpret_cast<uintptr_t>(vx->cell_u32) | reinterpret_cast<uintptr_t>(vx->n_u32)) & 3) != 0)
+            return fail(fn + "voxel count must start on an 8-byte boundary, cell_u32 and n_u32 on a 4-byte boundary");
+        if (rt_voxel_workspace_bytes(batch, (int)records, &vx->grid) == 0)
+            return fail(fn + "the batch or the grid is beyond rt_points_voxel_grid's limits (dims in [1, 4096], at most 2^27 cells, leaf finite and > 0, "
+                             "origin finite)");
+        struct Range { const void* p; size_t n; };
+        const size_t nb = (size_t)batch;
+        const Range outs[4] = {{vx->voxels, nb * vx->capacity * 16}, {vx->count, nb * 8}, {vx->cell_u32, nb * vx->capacity * 4}, {vx->n_u32, nb * vx->capacity * 4}};
+        const Range ins[2] = {{d->points ? d->points : d->points_compact, nb * (size_t)records * 16}, {d->points ? nullptr : d->count, nb * 8}};
+        const auto overlap = [](const Range& a, const Range& b) {
+            const uintptr_t x = reinterpret_cast<uintptr_t>(a.p), y = reinterpret_cast<uintptr_t>(b.p);
+            return a.p && b.p && x < y + b.n && y < x + a.n;
+        };
+        for (int i = 0; i < 4; i++) {
+            for (const Range& in : ins)
+                if (overlap(outs[i], in)) return fail(fn + "a voxel output overlaps the cloud it is made from");
+            for (int k = i + 1; k < 4; k++)
+                if (overlap(outs[i], outs[k])) return fail(fn + "two voxel outputs overlap");
+        }
     }
     const int H = net->height, W = net->width;
     const int bpp = c->encoding == RT_ENC_BGRA8 || c->encoding == RT_ENC_RGBA8 ? 4 : 3;
@@ -499,6 +531,11 @@ int run_frames(const std::string& fn, rtStereoNet* net, const FrameJob& j, rtStr
     // (rt_points_workspace_bytes is 0 for sizes the front end refuses below)
     if (d && (d->points_compact || d->count) && !net->points_ws.grow(rt_points_workspace_bytes(net->max_batch, c->src_h, c->src_w)))
         return fail(as + rt_last_error_string());
+    if (vx) {
+        const size_t records = (size_t)c->src_h * c->src_w;
+        if (!d->points && !d->points_compact && !net->voxel_cloud.grow((size_t)batch * records * 16)) return fail(as + rt_last_error_string());
+        if (!net->voxel_ws.grow(rt_voxel_workspace_bytes(batch, (int)records, &vx->grid))) return fail(as + rt_last_error_string());
+    }
     if (sp && !net->speckle_ws.p) {
         const size_t need = rt_speckle_workspace_bytes(net->max_batch, H, W);
         if (need == 0) return fail(as + "the network's size is beyond the speckle filter's limits");
@@ -544,11 +581,17 @@ int run_frames(const std::string& fn, rtStereoNet* net, const FrameJob& j, rtStr
             mask = net->frame_mask.p;
         }
         // (without a mask c->mask_u8 and c->valid_count are NULL: checked above)
-        if (rc == 0 && d)
+        if (rc == 0 && d) {
+            // the cloud the voxel grid is made from: the caller's organised one, else the caller's compact one, else the net's own (organised)
+            void* organised = d->points || !vx || d->points_compact ? d->points : net->voxel_cloud.p;
             rc = rt_disparity_to_points(px, mask, batch, H, W, c->src_h, c->src_w, &d->camera, d->min_depth, d->max_depth, c->left_u8, c->src_step,
-                                        c->encoding, c->disp, c->disp_kind, c->mask_u8, c->valid_count, d->depth, d->depth_kind, d->points,
+                                        c->encoding, c->disp, c->disp_kind, c->mask_u8, c->valid_count, d->depth, d->depth_kind, organised,
                                         d->points_compact, d->count, net->points_ws.p, net->points_ws.bytes, stream);
-        else if (rc == 0)
+            if (rc == 0 && vx)
+                rc = rt_points_voxel_grid(organised ? organised : d->points_compact, organised ? nullptr : d->count, batch, c->src_h * c->src_w, &vx->grid,
+                                          vx->min_points, vx->voxels, vx->capacity, vx->count, vx->cell_u32, vx->n_u32, net->voxel_ws.p,
+                                          net->voxel_ws.bytes, stream);
+        } else if (rc == 0)
             rc = rt_disparity_to_frame(px, mask, batch, H, W, c->disp, c->disp_kind, c->src_h, c->src_w, c->mask_u8, c->valid_count, stream);
     }
     if (rc != 0) return fail(as + rt_last_error_string());
@@ -662,6 +705,20 @@ extern "C" int rt_net_execute_frames_camera(rtStereoNet* net, const rtFrameCall*
     j.sp = speckle;
     j.dec = decode;
     return run_frames("rt_net_execute_frames_camera: ", net, j, stream);
+}
+
+// ... with the cloud put on a voxel grid: one rt_points_voxel_grid behind rt_disparity_to_points
+extern "C" int rt_net_execute_frames_voxels(rtStereoNet* net, const rtFrameCall* call, const rtDepthCall* out, const rtRectifyCall* rect,
+                                            const rtSpeckleCall* speckle, const rtDecodeCall* decode, const rtVoxelCall* voxel, rtStream stream) {
+    if (!voxel) return rt_net_execute_frames_camera(net, call, out, rect, speckle, decode, stream);
+    FrameJob j;
+    j.c = call;
+    j.d = out;
+    j.r = rect;
+    j.sp = speckle;
+    j.dec = decode;
+    j.vx = voxel;
+    return run_frames("rt_net_execute_frames_voxels: ", net, j, stream);
 }
 
 extern "C" int rt_net_profile(rtStereoNet* net, const void* left, const void* right, void* disp, int batch, char* buf,

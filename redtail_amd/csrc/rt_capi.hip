@@ -31,6 +31,7 @@
 #include "kernels/rectify.hip.h"
 #include "kernels/decode.hip.h"
 #include "kernels/speckle.hip.h"
+#include "kernels/voxel.hip.h"
 #include "kernels/conv_f16.hip.h"
 #include "kernels/conv_f16_first.hip.h"
 #include "kernels/conv_f16r4.hip.h"
@@ -1067,6 +1068,145 @@ extern "C" int rt_disparity_speckle(const void* disp_px, const void* mask_u8, in
                            static_cast<unsigned long long*>(valid_count));
     }
     RT_LAUNCH_CHECK("speckle_apply_kernel");
+    return 0;
+}
+
+// voxel grid of a cloud (voxel.hip.h): clear, mark, scan (blocks, sums), zero, accumulate, [scan of N >= min_points], emit.  The workspace
+// holds, for every image, five 64-bit sums per slot (slots = min(capacity, cells)), the bitmap and one prefix word per bitmap word, one
+// index word per slot, the two scans' block sums and two totals.
+namespace {
+struct VoxelLayout {
+    rt::VoxelArgs a{};
+    size_t acc = 0, bitmap = 0, prefix = 0, sums = 0, slot_prefix = 0, slot_sums = 0, totals = 0, bytes = 0;     // byte offsets, and the size
+};
+// false for what the op refuses in batch, capacity or grid
+bool voxel_layout(int batch, int capacity, const rtVoxelGrid* g, VoxelLayout* out) {
+    if (!g || batch < 1 || batch > 32767 || capacity < 1 || capacity > (1 << 23)) return false;
+    int64_t cells = 1;
+    for (int k = 0; k < 3; k++) {
+        if (g->dims[k] < 1 || g->dims[k] > 4096) return false;
+        if (!(g->leaf[k] > 0.f && g->leaf[k] <= 3.402823466e38f) || !(fabsf(g->origin[k]) <= 3.402823466e38f)) return false;       // (false for NaN too)
+        cells *= g->dims[k];
+    }
+    if (cells > ((int64_t)1 << 27)) return false;
+    VoxelLayout l;
+    for (int k = 0; k < 3; k++) { l.a.o[k] = g->origin[k]; l.a.leaf[k] = g->leaf[k]; l.a.dims[k] = g->dims[k]; }
+    l.a.capacity = capacity;
+    l.a.words = rt::cdiv(cells, 32);
+    l.a.slots = std::min<int64_t>(capacity, cells);
+    l.a.scan_blocks = (int)rt::cdiv(l.a.words, rt::kVoxelScan);
+    l.a.slot_blocks = (int)rt::cdiv(l.a.slots, rt::kVoxelScan);
+    const size_t n = (size_t)batch;
+    size_t at = 0;
+    l.acc = at;         at += n * (size_t)l.a.slots * rt::kVoxelAcc * sizeof(unsigned long long);
+    l.bitmap = at;      at += n * (size_t)l.a.words * sizeof(unsigned);
+    l.prefix = at;      at += n * (size_t)l.a.words * sizeof(unsigned);
+    l.sums = at;        at += n * (size_t)l.a.scan_blocks * sizeof(unsigned);
+    l.slot_prefix = at; at += n * (size_t)l.a.slots * sizeof(unsigned);
+    l.slot_sums = at;   at += n * (size_t)l.a.slot_blocks * sizeof(unsigned);
+    l.totals = at;      at += n * 2 * sizeof(unsigned);
+    l.bytes = at;
+    *out = l;
+    return true;
+}
+bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return a && b && x < y + nb && y < x + na;
+}
+}  // namespace
+
+extern "C" size_t rt_voxel_workspace_bytes(int batch, int capacity, const rtVoxelGrid* grid) {
+    VoxelLayout l;
+    return voxel_layout(batch, capacity, grid, &l) ? l.bytes : 0;
+}
+
+extern "C" int rt_points_voxel_grid(const void* points, const void* count, int batch, int capacity, const rtVoxelGrid* grid, int min_points,
+                                    void* voxels, int out_capacity, void* out_count, void* out_cell_u32, void* out_n_u32, void* workspace,
+                                    size_t workspace_bytes, rtStream s) {
+    const char* fn = "rt_points_voxel_grid";
+    RT_REQUIRE(points && grid && voxels && out_count, "%s: null pointer", fn);
+    RT_REQUIRE(batch >= 1 && batch <= 32767, "%s: batch %d outside [1, 32767]", fn, batch);
+    RT_REQUIRE(capacity >= 1 && capacity <= (1 << 23) && out_capacity >= 1 && out_capacity <= (1 << 23),
+               "%s: capacity %d and out_capacity %d must lie in [1, 2^23]", fn, capacity, out_capacity);
+    int64_t cells = 1;
+    for (int k = 0; k < 3; k++) {
+        RT_REQUIRE(grid->dims[k] >= 1 && grid->dims[k] <= 4096, "%s: dims[%d] = %d outside [1, 4096]", fn, k, grid->dims[k]);
+        cells *= grid->dims[k];
+    }
+    RT_REQUIRE(cells <= ((int64_t)1 << 27), "%s: a grid of %lld cells, more than 2^27", fn, (long long)cells);
+    for (int k = 0; k < 3; k++) {
+        RT_REQUIRE(grid->leaf[k] > 0.f && grid->leaf[k] <= 3.402823466e38f, "%s: leaf must be finite numbers > 0", fn);       // (false for NaN too)
+        RT_REQUIRE(fabsf(grid->origin[k]) <= 3.402823466e38f, "%s: origin must be finite", fn);
+    }
+    RT_REQUIRE(min_points >= 1, "%s: min_points must be >= 1", fn);
+    RT_REQUIRE(aligned16(points) && aligned16(voxels), "%s: a cloud must start on a 16-byte boundary", fn);
+    RT_REQUIRE(((reinterpret_cast<uintptr_t>(count) | reinterpret_cast<uintptr_t>(out_count)) & 7) == 0 &&
+               ((reinterpret_cast<uintptr_t>(out_cell_u32) | reinterpret_cast<uintptr_t>(out_n_u32)) & 3) == 0,
+               "%s: counts must start on an 8-byte boundary, out_cell_u32 and out_n_u32 on a 4-byte boundary", fn);
+    VoxelLayout l;
+    RT_REQUIRE(voxel_layout(batch, capacity, grid, &l), "%s: bad arguments", fn);
+    RT_REQUIRE(workspace && workspace_bytes >= l.bytes && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
+               "%s: workspace of %zu bytes, rt_voxel_workspace_bytes asks for %zu (8-byte aligned)", fn, workspace ? workspace_bytes : (size_t)0,
+               l.bytes);
+    {
+        const size_t nb = (size_t)batch;
+        const std::pair<const void*, size_t> in[2] = {{points, nb * capacity * 16}, {count, nb * 8}};
+        const std::pair<const void*, size_t> out[5] = {{voxels, nb * out_capacity * 16}, {out_count, nb * 8}, {out_cell_u32, nb * out_capacity * 4},
+                                                       {out_n_u32, nb * out_capacity * 4}, {workspace, l.bytes}};
+        for (const auto& i : in)
+            for (const auto& o : out) RT_REQUIRE(!overlaps(i.first, i.second, o.first, o.second), "%s: an output overlaps an input", fn);
+        for (int i = 0; i < 5; i++)
+            for (int j = i + 1; j < 5; j++)
+                RT_REQUIRE(!overlaps(out[i].first, out[i].second, out[j].first, out[j].second), "%s: two outputs overlap", fn);
+    }
+    char* ws = static_cast<char*>(workspace);
+    unsigned long long* acc = reinterpret_cast<unsigned long long*>(ws + l.acc);
+    unsigned* bitmap = reinterpret_cast<unsigned*>(ws + l.bitmap);
+    unsigned* prefix = reinterpret_cast<unsigned*>(ws + l.prefix);
+    unsigned* sums = reinterpret_cast<unsigned*>(ws + l.sums);
+    unsigned* slot_prefix = reinterpret_cast<unsigned*>(ws + l.slot_prefix);
+    unsigned* slot_sums = reinterpret_cast<unsigned*>(ws + l.slot_sums);
+    unsigned* totals = reinterpret_cast<unsigned*>(ws + l.totals);
+    const rt::VoxelArgs& a = l.a;
+    const uint4* src = static_cast<const uint4*>(points);
+    const unsigned long long* cnt = static_cast<const unsigned long long*>(count);
+    RT_HIP(hipMemsetAsync(out_count, 0, (size_t)batch * sizeof(unsigned long long), S(s)));
+    RT_HIP(hipMemsetAsync(bitmap, 0, (size_t)batch * (size_t)a.words * sizeof(unsigned), S(s)));
+    const dim3 per_run((unsigned)rt::cdiv(capacity, 256 * rt::kVoxelRun), (unsigned)batch);
+    hipLaunchKernelGGL(rt::voxel_mark_kernel, per_run, dim3(256), 0, S(s), a, src, cnt, bitmap);
+    RT_LAUNCH_CHECK("voxel_mark_kernel");
+    hipLaunchKernelGGL(rt::voxel_scan_kernel<false>, dim3((unsigned)a.scan_blocks, (unsigned)batch), dim3(256), 0, S(s), a,
+                       static_cast<const unsigned*>(bitmap), static_cast<const unsigned long long*>(acc), static_cast<const unsigned*>(totals), 0u,
+                       prefix, sums);
+    RT_LAUNCH_CHECK("voxel_scan_kernel");
+    hipLaunchKernelGGL(rt::voxel_scan_sums_kernel, dim3((unsigned)batch), dim3(256), 0, S(s), sums, a.scan_blocks, totals, 0);
+    RT_LAUNCH_CHECK("voxel_scan_sums_kernel");
+    hipLaunchKernelGGL(rt::voxel_zero_kernel, dim3((unsigned)rt::cdiv(a.slots * rt::kVoxelAcc, 256), (unsigned)batch), dim3(256), 0, S(s), a,
+                       static_cast<const unsigned*>(totals), acc);
+    RT_LAUNCH_CHECK("voxel_zero_kernel");
+    hipLaunchKernelGGL(rt::voxel_accumulate_kernel, per_run, dim3(256), 0, S(s), a, src, cnt, static_cast<const unsigned*>(bitmap),
+                       static_cast<const unsigned*>(prefix), static_cast<const unsigned*>(sums), acc);
+    RT_LAUNCH_CHECK("voxel_accumulate_kernel");
+    const dim3 per_word((unsigned)rt::cdiv(a.words, 256), (unsigned)batch);
+    auto emit = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, per_word, dim3(256), 0, S(s), a, static_cast<const unsigned*>(bitmap), static_cast<const unsigned*>(prefix),
+                           static_cast<const unsigned*>(sums), static_cast<const unsigned long long*>(acc), static_cast<const unsigned*>(slot_prefix),
+                           static_cast<const unsigned*>(slot_sums), static_cast<const unsigned*>(totals), (unsigned)min_points,
+                           static_cast<uint4*>(voxels), out_capacity, static_cast<unsigned long long*>(out_count),
+                           static_cast<unsigned*>(out_cell_u32), static_cast<unsigned*>(out_n_u32));
+    };
+    if (min_points > 1) {
+        hipLaunchKernelGGL(rt::voxel_scan_kernel<true>, dim3((unsigned)a.slot_blocks, (unsigned)batch), dim3(256), 0, S(s), a,
+                           static_cast<const unsigned*>(bitmap), static_cast<const unsigned long long*>(acc), static_cast<const unsigned*>(totals),
+                           (unsigned)min_points, slot_prefix, slot_sums);
+        RT_LAUNCH_CHECK("voxel_scan_kernel (min_points)");
+        hipLaunchKernelGGL(rt::voxel_scan_sums_kernel, dim3((unsigned)batch), dim3(256), 0, S(s), slot_sums, a.slot_blocks, totals, 1);
+        RT_LAUNCH_CHECK("voxel_scan_sums_kernel (min_points)");
+        emit(rt::voxel_emit_kernel<true>);
+    } else {
+        emit(rt::voxel_emit_kernel<false>);
+    }
+    RT_LAUNCH_CHECK("voxel_emit_kernel");
     return 0;
 }
 
